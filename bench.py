@@ -1,6 +1,7 @@
 """bench.py — headline benchmark (BASELINE.json metric) for the pattern-matching hot path.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--requests N]
+                  [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (ajx kernels behind authjx_eval_batch_device) over one
 batch of N synthetic Authorization-JSON documents already resident in HBM. N=1 runs the
@@ -14,6 +15,12 @@ JSON line. c4 (10k AuthConfigs, per-request set ids from the host index) and c5 
 phase, 4 KiB documents) default to 2M requests per GPU (16M over 8 GPUs).
 `--dry-run` runs the same distributed driver on the CPU (gloo) with a stand-in step, for
 the CPU tests of the N>1 path.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step,
+the roofline of the timed steps). `--dump-outputs DIR` also writes what the last timed
+step left in the output buffers (dump_outputs). `--full` adds every other leg: the oracle
+CPU baseline with its parity check, the c1 CPU figure, the PCIe-inclusive batch, c4's
+host lookup and serving leg, c5's phase decisions, the undecided and exact-path counts.
 """
 import argparse
 import json
@@ -52,7 +59,18 @@ def parse():
     ap.add_argument("--gather-decisions", action="store_true",
                     help="N>1: all-gather every rank's decision bitmap inside each step (SURVEY.md §8e, optional)")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "pmc_traffic.json"))
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output buffers of the last timed step as DIR/<name>.npy "
+                         "(see dump_outputs; a --dry-run has none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline value: CPU baseline and parity, c1, "
+                         "PCIe-inclusive, host lookup, serving, phase decisions, undecided / exact-path counts")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu = args.no_pcie = args.no_serve = True
+    return args
 
 
 def _free_port() -> int:
@@ -236,6 +254,48 @@ def timed_steps(step, steps, warmup, dist, torch, dev, stream=None):
     return elapsed, kern_ms
 
 
+DUMP_BUDGET = 60 * 1000 * 1000  # bytes over all files of one run, every rank's included
+
+
+def dump_outputs(out_dir, rank, world, tri, err, bm, spans=None) -> dict:
+    """Write what the timed path left in its caller's buffers after the last step, one row
+    per request, as out_dir/<name>.npy (rank k > 0: <name>_rank<k>.npy):
+      tri         f32 [rows][trees]      the tri-state result of every tree
+      err         f64 [rows][trees]      its error code
+      bitmap_u16  f32 [rows][4 * words]  the pattern bitmap, each 64-bit word as four 16-bit
+                                         quarters, least significant first (exact in f32)
+      spans       f64 [rows][selectors][3]  (c5) the response selectors' values
+    Every request when that fits DUMP_BUDGET; else a fixed, seeded sample of the rows, in
+    ascending order, whose indices go to sample_rows (f64). tri, err: [n][trees] device
+    tensors; bm: [n][words] int64; spans: [n][selectors][3] int32 or None."""
+    import torch
+
+    n = int(tri.shape[0])
+    row_bytes = 4 * tri.shape[1] + 8 * err.shape[1] + 16 * bm.shape[1] + 8
+    if spans is not None:
+        row_bytes += 8 * spans.shape[1] * spans.shape[2]
+    k = min(n, DUMP_BUDGET // max(1, world) // row_bytes)
+    rows = None
+    if k < n:
+        rows = np.sort(np.random.default_rng(20240229).choice(n, size=k, replace=False))
+        idx = torch.from_numpy(rows).to(tri.device)
+        tri, err, bm = tri[idx], err[idx], bm[idx]
+        spans = spans[idx] if spans is not None else None
+    out = {"tri": tri.cpu().numpy().astype(np.float32),
+           "err": err.cpu().numpy().astype(np.float64),
+           "bitmap_u16": np.ascontiguousarray(bm.cpu().numpy()).view("<u2").astype(np.float32)}
+    if spans is not None:
+        out["spans"] = np.ascontiguousarray(spans.cpu().numpy()).view(np.uint32).astype(np.float64)
+    if rows is not None:
+        out["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return {"dir": out_dir, "rows": k, "of": n, "files": sorted(name + suffix + ".npy" for name in out),
+            "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 def c1_cpu_ns_per_op(reps: int = 200000) -> dict:
     """BASELINE configs[0]: one ~700-byte document, All(eq, incl,
     matches), the oracle on ONE host thread, ns per Matches call (the analogue of the
@@ -390,6 +450,9 @@ def main():
     elapsed, kern_ms = timed_steps(step, args.steps, args.warmup, dist, torch, dev, stream)
     if gather:
         extra["decision_gather"] = gather.report()
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, rank, world, tri.view(w.n, nt), err.view(w.n, nt), bm, spans)
 
     total_req = w.n * args.steps * world
     value = int(rpr.sum()) * args.steps * world / elapsed  # shards are equal-sized (weak scaling)
@@ -419,8 +482,8 @@ def main():
         pass
 
     cpu, parity, c1, pcie = None, None, None, None
-    tri_h = tri.cpu().numpy()
-    if phase:
+    tri_h = tri.cpu().numpy() if args.full else None
+    if phase and args.full:
         # the phase decision from the per-tree results (auth_pipeline.go:454-457, :287-322)
         t = tri_h.reshape(w.n, nt)[:, :nt_out]  # (the last tree: response selectors)
         skipped = t[:, 0] != runtime.T
@@ -463,8 +526,8 @@ def main():
         dt = time.perf_counter() - t0
         extra["host_lookup"] = {"requests": w.n, "ms": dt * 1e3, "hosts_per_s": w.n / dt, "threads": nth,
                                 "equal_to_restatement": bool(np.array_equal(got, w.set_of_req.astype(np.int32)))}
-    undecided = int((tri_h == runtime.UNDECIDED).sum())
-    exact_path = ctx.last_exact_count()  # requests the single-pass kernel handed to the exact scan
+    undecided = int((tri_h == runtime.UNDECIDED).sum()) if args.full else None
+    exact_path = ctx.last_exact_count() if args.full else None  # requests the single-pass kernel handed to the exact scan
     if rank == 0 and world == 1 and not args.no_serve and w.set_of_req is not None and nt == 1:
         # the serving path (never the headline value): 64 native producer threads push a
         # sample of the batch through the micro-batcher one blocking request at a time, as
@@ -541,6 +604,7 @@ def main():
             "undecided": undecided,
             **extra,
             "exact_path_requests": exact_path,
+            **({"dumped_outputs": dumped} if dumped else {}),
         }
         print(json.dumps(line), flush=True)
     if dist:

@@ -2,7 +2,7 @@
 R=$GRAFT_REPO_ROOT; cd $R && O=gpurun_out/${OUT:-r05bench} && mkdir -p $O && export TMPDIR=/tmp
 for spec in ${SPECS:-"c2" "c2 --unique 1048576 --no-cpu --no-pcie" "c3 --no-pcie" "c4" "c5"}; do
   set -- $spec; wl=$1; shift; tag=$wl$(echo "$*" | tr -dc 'a-z0-9' | head -c 12)
-  timeout -k 10 500 python -u bench.py --workload $wl "$@" > $O/bench_$tag.log 2>&1 || { echo "bench $spec failed"; tail -20 $O/bench_$tag.log; exit 1; }
+  timeout -k 10 500 python -u bench.py --full --workload $wl "$@" > $O/bench_$tag.log 2>&1 || { echo "bench $spec failed"; tail -20 $O/bench_$tag.log; exit 1; }
   grep '"metric"' $O/bench_$tag.log | python3 -c "
 import sys, json
 for l in sys.stdin:

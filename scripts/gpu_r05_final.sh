@@ -10,7 +10,7 @@ tail -3 $O/pytest_gpu.log; grep -E "FAILED|ERROR" $O/pytest_gpu.log | head -20 |
 fi
 for spec in ${SPECS:-c2 c2u c3 c4 c5}; do
   wl=${spec%u}; extra=""; [ "$spec" != "$wl" ] && extra="--unique 1048576"
-  timeout -k 10 500 python -u bench.py --workload $wl $extra > $O/bench_$spec.log 2>&1 || { echo "bench $spec failed"; tail -20 $O/bench_$spec.log; exit 1; }
+  timeout -k 10 500 python -u bench.py --full --workload $wl $extra > $O/bench_$spec.log 2>&1 || { echo "bench $spec failed"; tail -20 $O/bench_$spec.log; exit 1; }
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_$spec -o $spec -- python3 $R/bench.py --no-cpu --no-pcie --no-serve --workload $wl $extra --steps 5 > $R/$O/prof_$spec.log 2>&1) || { echo "rocprof $spec failed"; exit 1; }
 done
 if [ -z "$NOPMC" ]; then

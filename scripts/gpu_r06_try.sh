@@ -7,7 +7,7 @@ tail -3 $O/pytest.log; grep -E "FAILED|ERROR" $O/pytest.log | head -10
 [ $rc -eq 0 ] || exit 1
 fi
 for wl in $BENCH_WLS; do
-  timeout -k 10 300 python -u bench.py --workload $wl --steps 10 --warmup 3 --cpu-seconds 3 --no-pcie --no-serve > $O/bench_$wl.log 2>&1 || { echo "bench $wl failed"; tail -20 $O/bench_$wl.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --workload $wl --steps 10 --warmup 3 --cpu-seconds 3 --no-pcie --no-serve > $O/bench_$wl.log 2>&1 || { echo "bench $wl failed"; tail -20 $O/bench_$wl.log; exit 1; }
   tail -1 $O/bench_$wl.log | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$wl', round(d['ms_per_step'],4), round(d['roofline']['kernel_ms'],4), d.get('parity'))"
 done
 for wl in $PMC_WLS; do

@@ -116,6 +116,63 @@ def test_decision_bitmap_layout():
     assert got.tolist() == [0b00101101, 0b10000000]
 
 
+def test_dump_outputs_files_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one row per request in f32 / f64 files that hold the buffers exactly
+    (the 64-bit bitmap words as 16-bit quarters, least significant first); over the byte
+    budget, the same seeded sample of rows on every call, named in sample_rows."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    n, nt, words, nsel = 1000, 3, 2, 2
+    rng = np.random.default_rng(11)
+    tri = rng.integers(0, 4, (n, nt), dtype=np.uint8)
+    err = rng.integers(-1, 2 ** 31 - 1, (n, nt), dtype=np.int32)
+    bm = rng.integers(0, 2 ** 64, (n, words), dtype=np.uint64)
+    bm[0] = [0x0123456789ABCDEF, 2 ** 64 - 1]
+    spans = rng.integers(0, 2 ** 32, (n, nsel, 3), dtype=np.uint32)
+    dev = [torch.from_numpy(a) for a in (tri, err, bm.view(np.int64), spans.view(np.int32))]
+
+    rep = bench.dump_outputs(str(tmp_path / "all"), 0, 1, *dev)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in rep["files"]}
+    assert sorted(got) == ["bitmap_u16", "err", "spans", "tri"] and rep["rows"] == rep["of"] == n
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["tri"], tri) and np.array_equal(got["err"], err) and np.array_equal(got["spans"], spans)
+    assert got["bitmap_u16"][0].tolist() == [0xCDEF, 0x89AB, 0x4567, 0x0123, 0xFFFF, 0xFFFF, 0xFFFF, 0xFFFF]
+    q = got["bitmap_u16"].astype(np.uint64).reshape(n, words, 4)
+    sh = np.array([0, 16, 32, 48], dtype=np.uint64)
+    assert np.array_equal(np.bitwise_or.reduce(q << sh, axis=-1), bm)
+
+    row_bytes = 4 * nt + 8 * nt + 16 * words + 8 + 8 * nsel * 3
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 100 * row_bytes)  # two ranks, 100 rows each
+    r1 = bench.dump_outputs(str(tmp_path / "s1"), 1, 2, *dev)
+    r2 = bench.dump_outputs(str(tmp_path / "s2"), 1, 2, *dev)
+    assert r1["rows"] == 100 and r1["bytes"] <= 100 * row_bytes and r1["files"] == r2["files"]
+    assert "sample_rows_rank1.npy" in r1["files"] and "tri_rank1.npy" in r1["files"]
+    rows = np.load(tmp_path / "s1" / "sample_rows_rank1.npy").astype(np.int64)
+    assert len(set(rows.tolist())) == 100 and np.all(np.diff(rows) > 0) and rows.max() < n
+    for f in r1["files"]:
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+    assert np.array_equal(np.load(tmp_path / "s1" / "tri_rank1.npy"), tri[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "spans_rank1.npy"), spans[rows])
+
+
+def test_plain_run_skips_the_full_legs(monkeypatch):
+    """Without --full the CPU baseline, PCIe-inclusive and serving legs are off whatever the
+    other options say; --full leaves them to --no-cpu / --no-pcie / --no-serve."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu and a.no_pcie and a.no_serve
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-pcie", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and not a.no_cpu and a.no_pcie and not a.no_serve and a.dump_outputs == "d"
+
+
 @pytest.mark.gpu
 def test_decision_bitmap_on_device():
     """The bitmap bench.py all-gathers, built by the same torch ops on the GPU."""
@@ -146,7 +203,7 @@ def test_bench_rccl_gather_one_rank_on_device():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--gather-decisions", "--steps", "2", "--warmup", "1", "--requests", "65536",
-           "--cpu-seconds", "2", "--no-pcie"]
+           "--cpu-seconds", "2", "--no-pcie", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

@@ -26,7 +26,7 @@ def test_bench_rccl_world1_gather_decisions():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
            "--gather-decisions", "--steps", "2", "--warmup", "1", "--requests", "65536", "--no-pcie",
-           "--cpu-seconds", "1"]
+           "--cpu-seconds", "1", "--full"]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
