@@ -157,9 +157,12 @@ struct KeySlot {
     uint64_t sig;       // key_signature(key)
     uint32_t meta;      // key_len | parent << 16 | node << 24; kEmptySlot = free
     uint16_t key_off8;  // key bytes in the literal pool, / 8 (keys are 8-byte aligned)
-    uint16_t pad;
+    uint16_t facts;     // the child node's facts (kSlot*): the lean walk reads no TrieNode for it
 };
 static_assert(sizeof(KeySlot) == 16, "KeySlot layout");
+// KeySlot::facts, of the slot's child node: its selector + 1 (0 none; selectors are < 64),
+// it has children, it has array-index children (TrieNode::selector, n_children, flags bit 0)
+constexpr uint32_t kSlotSelMask = 0x7Fu, kSlotKids = 0x80u, kSlotArrKids = 0x100u;
 constexpr uint32_t kEmptySlot = 0xFFFFFFFFu;
 constexpr uint32_t kMaxKeySlotsLog2 = 9;
 constexpr uint32_t kKeyProbes = 4;  // the table is grown until every key is this close to home

@@ -825,6 +825,10 @@ int compile_core(const authjx_tree* tree, const std::vector<int32_t>& roots, boo
                 out[at].sig = e.sig;
                 out[at].meta = e.len | (e.parent << 16) | (e.node << 24);
                 out[at].key_off8 = (uint16_t)(e.key_off / 8u);  // (a pool past 512 KiB: no fast path, below)
+                // (the child's facts ride in the slot: tn[] is complete here, flags included)
+                const TrieNode& cn = tn[e.node];
+                out[at].facts = (uint16_t)(((uint32_t)(cn.selector + 1) & kSlotSelMask) |
+                                           (cn.n_children ? kSlotKids : 0u) | ((cn.flags & 1u) ? kSlotArrKids : 0u));
                 worst = std::max(worst, dist);
             }
             return worst;

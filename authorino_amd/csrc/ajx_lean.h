@@ -72,9 +72,10 @@ enum : uint32_t { S_RUN = 0, S_DONE = 1, S_SLOW = 2 };
 // The walker of one document. ARR: the ruleset has array-index selectors (arrays on
 // selector paths are walked element by element; without, every array is squashed: no
 // selector can match inside one); CAPS: a selector's value can be a container the walk
-// enters (a selector that is a prefix of another). The lean kernel takes the instance the
-// ruleset needs (RulesetHdr::lean_feat, kLeanArr / kLeanCaps); the fewer features, the less
-// state and code per iteration.
+// enters (a selector that is a prefix of another). The fewer features, the less state and
+// code per iteration. The lean kernel picks ARR by the ruleset's need (RulesetHdr::lean_feat,
+// kLeanArr) and always runs CAPS = true (launch_lean, ajx_lean.hip: the capture-free
+// instances measured slower); the compiler still records kLeanCaps in lean_feat.
 template <bool ARR = true, bool CAPS = true>
 struct Walk {
     // tables
@@ -134,6 +135,14 @@ struct Walk {
 #endif
         return (uint64_t)lo | ((uint64_t)hi << 32);
     }
+    // some lane of the wave (the host builds: this document)
+    AJX_HD static bool any_lane(bool x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_ballot_w64(x) != 0;
+#else
+        return x;
+#endif
+    }
     AJX_HD uint32_t node_at(uint32_t dd) const {  // 1..16
         const uint32_t k = dd - 1;
         const uint64_t w = k < 8 ? nlo : nhi;
@@ -148,14 +157,22 @@ struct Walk {
     // a captured value of selector s: doc [start, end), gjson type, has escapes. The
     // selector's eager patterns (EagerSel) are decided on an unescaped string's contents or
     // a literal's String() ("true", "false", ""); the capture record goes to the row unless
-    // they were every pattern of the selector (and no caller reads it back: kEagerKeep)
-    AJX_HD void record(int32_t s, uint32_t start, uint32_t end, uint32_t type, uint32_t esc) {
+    // they were every pattern of the selector (and no caller reads it back: kEagerKeep).
+    // v0: the value's first 8 bytes (from start: a string's opening quote and 7 bytes of its
+    // content), which the walk read with the token's other ring bytes (not looked at for
+    // other types). The content's other 9 bytes are read here, together with eg[s] (one LDS
+    // latency for both; holding them over the key lookup as well cost the walk loop
+    // spilled registers)
+    AJX_HD void record(int32_t s, uint32_t start, uint32_t end, uint32_t type, uint32_t esc, uint64_t v0 = 0) {
         found |= 1ull << s;
         bool dec = false;
         const bool lit = type == T_TRUE || type == T_FALSE || type == T_NULL;
         if (eg && ((type == T_STRING && !esc) || lit)) {
             const EagerSel e = eg[s];
-            const uint32_t mt = lit ? lit_match(e, type) : eager_match(e, start + 1u, end - start - 2u);
+            const uint64_t v1 = r64((start + 8u + mis) & 127u);
+            const uint64_t b16 = rb(start + 16u);
+            const uint64_t c0 = (v0 >> 8) | (v1 << 56), c1 = (v1 >> 8) | (b16 << 56);
+            const uint32_t mt = lit ? lit_match(e, type) : eager_match(e, end - start - 2u, c0, c1);
 #pragma unroll
             for (int k = 0; k < 2; k++) {
                 const uint32_t m = e.m[k], op = (m >> 8) & 0xFFu;
@@ -185,14 +202,10 @@ struct Walk {
         }
         return r;
     }
-    // bit k: entry k's literal equals the string content [a, a + cl) (ring bytes; cl <= 16
-    // for a match, and then the content lies in the ring's window)
-    AJX_HD uint32_t eager_match(const EagerSel& e, uint32_t a, uint32_t cl) const {
-        uint64_t c0 = 0, c1 = 0;
-        if (cl <= 16) {
-            c0 = r64((a + mis) & 127u);
-            c1 = r64((a + 8u + mis) & 127u);
-        }
+    // bit k: entry k's literal equals the string content of cl bytes whose first 16 bytes
+    // are c0, c1 (ring bytes; cl <= 16 for a match, and then the content lay in the ring's
+    // window when the walk read them)
+    AJX_HD static uint32_t eager_match(const EagerSel& e, uint32_t cl, uint64_t c0, uint64_t c1) {
         const uint64_t m0 = cl >= 8 ? ~0ull : ((1ull << (8 * cl)) - 1ull);
         const uint64_t m1 = cl >= 16 ? ~0ull : (cl > 8 ? ((1ull << (8 * (cl - 8))) - 1ull) : 0ull);
         uint32_t r = 0;
@@ -206,7 +219,8 @@ struct Walk {
         }
         return r;
     }
-    // the key table: (sig, len, parent) -> child node (kNoNode none). len = kIdxKeyLen:
+    // the key table: (sig, len, parent) -> child node (kNoNode none) | the child's facts << 8
+    // (KeySlot::facts; 0 with no node). len = kIdxKeyLen:
     // sig is an array index. A hit on a key longer than 8 bytes also compares its head
     // (bytes [ks, len - 8) of the key, starting at doc position ks) from the ring: the walk
     // looks a key up in the sub-window holding its closing quote, and the ring still holds
@@ -221,14 +235,25 @@ struct Walk {
         const bool longk = len > 8 && len != kIdxKeyLen;
         uint32_t node = kNoNode;
         for (uint32_t t = 0; t < ks_probes; t++) {
-            const KeySlot sl = ks[(h + t) & ks_mask];
-            bool hit = sl.meta != kEmptySlot && sl.sig == sig && (sl.meta & 0xFFFFFFu) == want;
+            // (the slot as one aligned 16-byte read: field by field, the compiler read its
+            // meta word first and its signature only after a test of that, two LDS latencies
+            // in a row. The key table is 16-byte aligned in the blob, and the blob in LDS)
+            struct alignas(16) SlotHalves {
+                uint64_t sig, rest;  // rest: meta | key_off8 << 32 | facts << 48
+            };
+            const SlotHalves q = *reinterpret_cast<const SlotHalves*>(&ks[(h + t) & ks_mask]);
+            KeySlot sl;
+            sl.sig = q.sig;
+            sl.meta = (uint32_t)q.rest;
+            sl.key_off8 = (uint16_t)(q.rest >> 32);
+            sl.facts = (uint16_t)(q.rest >> 48);
+            bool hit = (sl.meta != kEmptySlot) & (sl.sig == sig) & ((sl.meta & 0xFFFFFFu) == want);
             // (keys sharing their last 8 bytes, length and parent sit in later slots)
             if (hit && longk) {
                 const uint8_t* kl = lits + (uint32_t)sl.key_off8 * 8u;
                 hit = (int32_t)kstart >= ring_lo ? key_head_equal(kstart, len - 8, kl) : key_rest_equal(kstart, len - 8, kl);
             }
-            node = hit ? sl.meta >> 24 : node;
+            node = hit ? (sl.meta >> 24) | ((uint32_t)sl.facts << 8) : node;
         }
         return node;
     }
@@ -281,19 +306,22 @@ struct Walk {
         return (bs & m) != 0;
     }
 
-    // the trie node's facts (kNoNode: none): selector (-1 none) | n_children << 16 | flags << 24
+    // the trie node's facts as a key slot carries them for its child (KeySlot::facts, kSlot*;
+    // kNoNode: 0), for the nodes that no slot was read for: the root, a pending value's node
     AJX_HD uint32_t node_facts(uint32_t node) const {
-        if (node == kNoNode) return 0xFFFFu;
+        if (node == kNoNode) return 0u;
         const TrieNode t = tn[node];
-        return (uint32_t)(uint16_t)t.selector | (uint32_t)t.n_children << 16 | (uint32_t)t.flags << 24;
+        return ((uint32_t)(t.selector + 1) & kSlotSelMask) | (t.n_children ? kSlotKids : 0u) |
+               ((t.flags & 1u) ? kSlotArrKids : 0u);
     }
     // a container value at p ('{' or '['): node and its facts (node_facts)
     AJX_HD void open_f(uint32_t node, uint32_t nf, bool arr, uint32_t p) {
-        int32_t s = (int32_t)(int16_t)(nf & 0xFFFFu);
+        int32_t s = (int32_t)(nf & kSlotSelMask) - 1;
         if (s >= 0 && ((found >> s) & 1)) s = -1;
         // squashed (captured when a leaf): off every selector path, and arrays whose node
-        // has no array-index children (gjson matches no key inside an array)
-        if (node == kNoNode || (nf >> 16 & 0xFFu) == 0 || (arr && !((nf >> 24) & 1u))) {
+        // has no array-index children (gjson matches no key inside an array). So every
+        // array on the stack has a node with array-index children: its elements are looked up
+        if (node == kNoNode || !(nf & kSlotKids) || (arr && !(nf & kSlotArrKids))) {
             skipw = 1u | ((s >= 0 ? (uint32_t)s + 1u : 0u) << 24);
             skips = p;
             return;
@@ -328,8 +356,10 @@ struct Walk {
 
     // Walk sub-window c (l: the one after it; its tokens may be taken here: l.tok updated).
     // One iteration takes one token of every lane, whatever its kind, through ONE copy of
-    // each step: the token's kind decoded into flags, one key-table lookup (a key's last 8
-    // bytes and length, or an element's index), one node read, the value's first byte, its
+    // each step: the token's kind decoded into flags, one group of ring reads (the key's last
+    // 8 bytes, the value's first byte and first 16 content bytes), one key-table lookup (a
+    // key's last 8 bytes and length, or an element's index; the slot carries the child
+    // node's facts, so no trie node is read after it), the value's
     // end (a string's closing quote from the masks, a scalar's next structural byte), one
     // capture record (with the eager patterns), one open and one close. The lanes of a wave
     // hold tokens of different kinds in most iterations, so a walker with a code path per
@@ -370,6 +400,14 @@ struct Walk {
         const uint32_t cb = (uint32_t)c.base;
         const uint64_t cl64 = (uint64_t)c.cl | ((uint64_t)l.cl << 32);
         constexpr uint32_t kNone = 0xFFFFFFFFu;
+        // escapes are rare: has_bs is skipped, as a branch of the whole wave, unless some lane
+        // has a backslash in c or l, or one before c inside the string that is open at c's
+        // start (every string that starts before c starts at carry_oq, a pending value too)
+#if defined(AJX_LEAN_AB_NO_BSGUARD)  // (A/B builds: DESIGN §5.8)
+        const bool bsw = true;
+#else
+        const bool bsw = any_lane((c.bs | l.bs) != 0 || lbs1 > carry_oq);
+#endif
         AJX_LEAN_TICK(g_lean_subs);
         while (T) {
             AJX_LEAN_TICK(g_lean_iters);
@@ -391,23 +429,41 @@ struct Walk {
                 const uint32_t oqb = c.oq & below(i);
                 const uint32_t ss = oqb ? cb + hib(oqb) : carry_oq;
                 const uint32_t k0 = ss + 1u, klen = p - k0;
-                if (key && !bad) bad = klen >= kIdxKeyLen || has_bs(k0, p, c, l);
+                // the value's start vs (a string's opening quote)
+                const uint32_t vs = key ? p + 2u : pv ? (pend & 0xFFFFFFu) : bq ? ss : p;
+                // The token's ring bytes, read together before any table is (their positions
+                // come from the masks alone, so one LDS latency covers them all; a lane that
+                // turns out not to need some of them has read them for nothing): the key's
+                // last 8 bytes and the value's first 8 (a string's from its opening quote).
+                uint64_t sig = r64((p - 8u + mis) & 127u);
+                const uint64_t v0 = r64((vs + mis) & 127u);
+                // the value's first byte (a string element's or a pending value's opening
+                // quote may have left the ring: it is a quote)
+                const uint32_t vb = bq && !key ? (uint32_t)'"' : (uint32_t)v0 & 0xFFu;
+                if (key && !bad) bad = klen >= kIdxKeyLen || (bsw && has_bs(k0, p, c, l));
                 // the key table: a key's (last 8 bytes, length, parent) or an element's index
-                uint32_t node = kNoNode;
-                const bool eidx = ARR && el && top != kNoNode && (tn[top].flags & 1);
+                // (an array is on the stack only when its node has array-index children: open_f)
+                uint32_t lk = kNoNode;
+                const bool eidx = ARR && el;
                 if ((key && !bad) || eidx) {
-                    uint64_t sig = r64((p - 8u + mis) & 127u);
                     sig = klen >= 8 ? sig : (klen ? sig >> (8 * (8 - klen)) : 0ull);
-                    node = lookup(key ? sig : (uint64_t)idx, key ? klen : kIdxKeyLen, top, k0, (int32_t)cb - 32);
+                    lk = lookup(key ? sig : (uint64_t)idx, key ? klen : kIdxKeyLen, top, k0, (int32_t)cb - 32);
                 }
                 idx += el ? 1u : 0u;
+                // the node and its facts: from the key slot; from the trie only where no slot
+                // was read (a pending value's node, the root)
+                uint32_t node = lk & 0xFFu, nf = lk >> 8;
+#if defined(AJX_LEAN_AB_TN_FACTS)  // (A/B builds: DESIGN §5.8)
                 node = pv ? pend >> 24 : root ? 0u : node;
-                const uint32_t nf = node_facts(node);
-                int32_t s = (int32_t)(int16_t)(nf & 0xFFFFu);
+                nf = node_facts(node);
+#else
+                if (pv || root) {
+                    node = pv ? pend >> 24 : 0u;
+                    nf = node_facts(node);
+                }
+#endif
+                int32_t s = (int32_t)(nf & kSlotSelMask) - 1;
                 if (s >= 0 && ((found >> s) & 1)) s = -1;
-                // the value: start vs (a string's opening quote), first byte vb
-                const uint32_t vs = key ? p + 2u : pv ? (pend & 0xFFFFFFu) : bq ? ss : p;
-                const uint32_t vb = rb(key ? p + 2u : p);
                 const bool vstr = bq && (!key || vb == '"');
                 const bool vopen = key ? (vb == '{' || vb == '[') : bo;
                 const bool vscal = !bq && !bo && !bc ? true : key && !vstr && !vopen;
@@ -434,7 +490,7 @@ struct Walk {
                 // a scalar: gjson's value-start bytes, its end (the next structural byte), literals
                 uint32_t type = T_STRING, end = e + 1u;
                 if (vscal && !bad) {
-                    const bool lit = vb == 't' || vb == 'f' || (vb == 'n' && rb(vs + 1) == 'u');
+                    const bool lit = vb == 't' || vb == 'f' || (vb == 'n' && ((uint32_t)v0 >> 8 & 0xFFu) == 'u');
                     const uint32_t r = vs - cb;  // (< 64)
                     const uint64_t stm = (uint64_t)c.st | ((uint64_t)l.st << 32);
                     const uint64_t m = r >= 63 ? 0ull : stm & (~0ull << (r + 1));
@@ -446,7 +502,7 @@ struct Walk {
                         const uint32_t len = end - vs;
                         type = T_NUMBER;
                         if (lit) {
-                            const uint64_t w = r64((vs + mis) & 127u);
+                            const uint64_t w = v0;  // (a scalar's bytes from vs)
                             const bool ok = vb == 't' ? len == 4 && (uint32_t)w == 0x65757274u
                                           : vb == 'f' ? len == 5 && (w & 0xFFFFFFFFFFull) == 0x65736C6166ull
                                                       : len == 4 && (uint32_t)w == 0x6C6C756Eu;
@@ -458,7 +514,7 @@ struct Walk {
                 }
                 // the capture record (one site for every kind of value)
                 if (!bad && s >= 0 && ((vstr && ended) || vscal))
-                    record(s, vs, end, type, vstr && has_bs(vs, e, c, l) ? 1u : 0u);
+                    record(s, vs, end, type, vstr && bsw && has_bs(vs, e, c, l) ? 1u : 0u, v0);
                 // a container value
                 if (!bad && vopen) {
                     if (key) {

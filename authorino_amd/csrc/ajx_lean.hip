@@ -16,7 +16,8 @@ constexpr uint32_t kLeanMaxBlock = 1024;
 #endif
 
 // The lean single-pass kernel (ajx_lean.h): stage A with the lean scan, then stage B in the
-// same work-item. Dynamic LDS: [blob copy (SHARED)] [per wave: 64 lanes x 144-B rings].
+// same work-item. Dynamic LDS: [blob copy (SHARED)] [per wave: 64 lanes x 128-B rings,
+// chunk-major (lean::kRingStride, kChunkStride)].
 #ifndef AJX_LEAN_WAVES
 #define AJX_LEAN_WAVES AJX_FAST_WAVES  // waves per SIMD the lean kernel's registers are set for
 #endif
@@ -24,7 +25,8 @@ constexpr uint32_t kLeanMaxBlock = 1024;
 #define AJX_LEAN_MAXBLOCK kLeanMaxBlock
 #endif
 // ABL: profiling ablations (kernel modes 15..18, lean::scan_doc): stage A cut short, no stage B.
-// FEAT: the walker features the ruleset needs (RulesetHdr::lean_feat: kLeanArr | kLeanCaps)
+// FEAT: the walker features of the instance (kLeanArr | kLeanCaps). launch_lean picks by the
+// ruleset's kLeanArr alone (RulesetHdr::lean_feat): every instance it launches has kLeanCaps
 template <bool SHARED, int ABL = 0, int FEAT = 3>
 __global__ __launch_bounds__(AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES) void ajx_scan_lean(
     const uint8_t* const* __restrict__ sets, const uint32_t* __restrict__ set_of_req,
@@ -112,9 +114,11 @@ hipError_t launch_lean(const uint8_t* const* d_sets, uint32_t shared_blob_bytes,
     const uint32_t lgrid = (n + lblock - 1) / lblock;
     const uint32_t llds = ring_off + (lblock / 64) * lean::kRingBytesPerWave;
     const uint32_t keep = (keep_rows ? 1u : 0u) | (out_k && d_perm ? 2u : 0u);
-    // (two instances: without and with array walking. The capture-free instances cost
-    // the walk loop scratch reloads of spilled scalar registers, which wait behind the
-    // ring's loads in flight: measured slower, c2 1.39 against 1.27 ms)
+    // (two instances, FEAT 2 and 3: without and with array walking, by the ruleset's
+    // kLeanArr. Its kLeanCaps bit is not looked at: both instances enter captured containers,
+    // whether the ruleset needs that or not. The capture-free instances cost the walk loop
+    // scratch reloads of spilled scalar registers, which wait behind the ring's loads in
+    // flight: measured slower, c2 1.39 against 1.27 ms)
     const uint32_t feat = (lean_feat & kLeanArr) ? 3u : 2u;
     using K = void (*)(const uint8_t* const*, const uint32_t*, const uint8_t*, const uint64_t*, const uint32_t*,
                        uint32_t, uint64_t*, uint32_t, uint32_t*, uint32_t*, uint8_t*, int32_t*, uint64_t*, uint32_t,

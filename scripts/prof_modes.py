@@ -6,7 +6,8 @@ Modes (ajx_api.cpp / ajx_kernels.hip): 0 the product path; 15..18 the lean kerne
 ablations (15 loads + ring stores, 16 + classification, 17 + walk without eager patterns,
 18 full stage A), no stage B. Under `rocprofv3 --pmc ...` each mode's kernel instance has
 its own name (ajx_scan_lean<true, ABL>), so one counter pass covers every mode.
-Prints one JSON line per mode: mean HIP-event ms per launch on the eval stream.
+Prints one JSON line per mode: HIP-event ms per launch on the eval stream (mean, and the
+min / median / max of the launches).
 """
 import argparse
 import json
@@ -69,8 +70,10 @@ def main():
             ctx.eval_device(rss, arena, offs, lens, tri, err, bm, set_of_req=sor, stream=stream.cuda_stream)
             e1.record(stream)
         torch.cuda.synchronize(dev)
-        ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev]))
+        each = [e0.elapsed_time(e1) for e0, e1 in ev]
+        ms = float(np.mean(each))
         line = {"workload": a.workload, "n": w.n, "mode": m, "ms": round(ms, 4), "alias": a.alias,
+                "min": round(min(each), 4), "median": round(float(np.median(each)), 4), "max": round(max(each), 4),
                 "bytes": int(w.lens.astype(np.int64).sum())}
         if m == 0:
             ref = tri.cpu().numpy().copy()
