@@ -119,11 +119,7 @@ struct authjx_ctx {
     // batches of up to this many requests go to the streaming kernel (latency: several
     // waves per document span), larger ones to the lean / multi-tenant kernels
     uint32_t stream_max_n = 4096;
-    int ablate = 0;  // profiling / comparison only: 41 the lean single-pass kernel where the
-                     // streaming kernel would run, 52 the streaming kernel for a one-ruleset
-                     // batch of any size, 50 / 51 its structural pass alone / without its
-                     // fold, 53 its small-batch phase clocks (over the bitmap), 1..3 /
-                     // 10..12 token-scanner ablations and workgroup sizes
+    int mode = ajx::kModeDefault;  // profiling / comparison only: an ajx::KernelMode (ajx_plan.h)
 };
 
 namespace {
@@ -531,18 +527,34 @@ static int eval_device(authjx_ctx* ctx, const authjx_ruleset* const* sets, uint3
         if (w > need_words) need_words = w;
         if (sets[i]->c.n_selectors > max_sel) max_sel = sets[i]->c.n_selectors;
     }
-    const uint32_t row_stride = 1 + max_sel;
     if (d_out_bitmap && bitmap_stride_words < need_words) return AUTHJX_EINVAL;
-    int force_scan, ablate, len_sort, no_tenant_stage;
-    uint32_t stream_max_n;
+    // what the choice of kernels reads (ajx_plan.h): the batch's shape, its rulesets, the settings
+    ajx::PlanIn in{};
+    in.n = n;
+    in.n_sets = n_sets;
+    in.all_stream = 1;
+    in.max_sel = max_sel;
+    for (uint32_t i = 0; i < n_sets; i++) {
+        const auto* h = reinterpret_cast<const ajx::RulesetHdr*>(sets[i]->c.blob.data());
+        in.all_stream = in.all_stream && sets[i]->stream_ok;
+        in.max_rec = std::max(in.max_rec, sets[i]->stream_rec);
+        in.max_blob = std::max(in.max_blob, (uint32_t)sets[i]->c.blob.size());
+        // modifier chains: the exact scan's instance with text buffers
+        in.mods = in.mods || h->n_modifiers != 0 || (h->flags & ajx::kFlagBufs) != 0;
+    }
+    const auto* h0 = reinterpret_cast<const ajx::RulesetHdr*>(sets[0]->c.blob.data());
+    in.n_trees = h0->pad1[0];
+    in.lean_feat = h0->lean_feat;
+    in.bitmap = d_out_bitmap != nullptr;
     {
         std::lock_guard<std::mutex> g(ctx->mu);
-        force_scan = ctx->force_scan;
-        ablate = ctx->ablate;
-        len_sort = ctx->len_sort;
-        no_tenant_stage = ctx->no_tenant_stage;
-        stream_max_n = ctx->stream_max_n;
+        in.force_scan = ctx->force_scan;
+        in.mode = ctx->mode;
+        in.len_sort = ctx->len_sort;
+        in.no_tenant_stage = ctx->no_tenant_stage;
+        in.stream_max_n = ctx->stream_max_n;
     }
+    const ajx::EvalPlan plan = ajx::plan_eval(in);
     WsLock wl(ctx, stream);
     Workspace* w = wl.w;
     if (!w) return AUTHJX_EDEVICE;
@@ -550,94 +562,45 @@ static int eval_device(authjx_ctx* ctx, const authjx_ruleset* const* sets, uint3
     HIP_OK(hipSetDevice(ctx->device));
     int rc = ensure_sets(w, ctx->device, sets, n_sets, d_sets_pre);
     if (rc != AUTHJX_OK) return rc;
-    // the streaming kernel: small batches (latency; one request per wave for a multi-tenant
-    // batch) whose rulesets all have stream tables; any one-ruleset batch under kernel
-    // mode 50..52 (its rows carry 4 more words: the eager decisions stage B reads)
-    bool all_stream = true;
-    for (uint32_t i = 0; i < n_sets; i++) all_stream = all_stream && sets[i]->stream_ok;
-    const bool small = n <= stream_max_n;
-    const bool use_stream = !force_scan && all_stream &&
-                            (((ablate == 0 || ablate == 53) && small) || (n_sets == 1 && ablate >= 50 && ablate <= 52));
-    // requests per wave: 32 for throughput, fewer for a small batch (more waves share it)
-    uint32_t per = ajx::kStreamSpan;
-    if (n_sets > 1)
-        per = 1;
-    else if (ablate == 0 || ablate == 53)
-        per = std::max<uint32_t>(1u, std::min<uint32_t>(ajx::kStreamSpan, (n + 2047u) / 2048u));
-    uint32_t max_rec = 0;
-    for (uint32_t i = 0; i < n_sets; i++) max_rec = std::max(max_rec, sets[i]->stream_rec);
-    const uint32_t rows_stride = use_stream ? std::max(row_stride, 1u + max_rec) + 4u : row_stride;
-    if (!force_scan) {
-        rc = ensure_work(w, n, rows_stride);
+    if (plan.path != ajx::kPathExact) {
+        rc = ensure_work(w, n, plan.rows_stride);
         if (rc != AUTHJX_OK) return rc;
     }
     HIP_OK(hipEventRecord(w->ev0, s));
-    // kernel: the streaming kernel (ajx_stream.h) for a one-ruleset batch whose ruleset it
-    // takes, else the lean single-pass kernel (ajx_lean.h) or the multi-tenant kernel; the
-    // exact scan for what they hand over
-    bool mods = false;  // modifier chains: the exact scan's instance with text buffers
-    for (uint32_t i = 0; i < n_sets; i++)
-        mods = mods || reinterpret_cast<const ajx::RulesetHdr*>(sets[i]->c.blob.data())->n_modifiers != 0 ||
-               (reinterpret_cast<const ajx::RulesetHdr*>(sets[i]->c.blob.data())->flags & ajx::kFlagBufs) != 0;
-    // capture rows kept for authjx_select_from_eval_device: one forest ruleset
-    // (authjx_compile_forest), a full kernel
-    const bool full = ablate == 0 || ablate == 41 || ablate == 52 || (ablate >= 10 && ablate <= 12) ||
-                      (ablate >= 15 && ablate <= 18);  // (15..18: lean ablations, length order kept)
-    const auto* h0 = reinterpret_cast<const ajx::RulesetHdr*>(sets[0]->c.blob.data());
-    // (not under the lean ablations 15..18: their rows hold checksums)
-    const bool keep_rows = !force_scan && n_sets == 1 && full && !(ablate >= 15 && ablate <= 18) && h0->pad1[0] != 0;
-    w->rows_rs = keep_rows ? sets[0] : nullptr;
+    // capture rows kept for authjx_select_from_eval_device
+    w->rows_rs = plan.keep_rows ? sets[0] : nullptr;
     w->rows_n = n;
-    w->rows_stride = row_stride;
+    w->rows_stride = plan.rows_stride;
     w->rows_perm = nullptr;
     w->rows_wave = true;
-    size_t max_blob = 0;
-    for (uint32_t i = 0; i < n_sets; i++) max_blob = std::max(max_blob, sets[i]->c.blob.size());
     // (the counters are zero only after a FIN launch: every other launch fills them itself)
     bool cnt_zero = w->cnt_zero;
     w->cnt_zero = w->exact3 = false;
-    if (force_scan) {
-        HIP_OK(ajx::launch_eval_scan(w->d_sets, d_set_of_req, d_arena, d_offs, d_lens, n, d_out_tristate,
-                                     d_out_err_idx, d_out_bitmap, bitmap_stride_words, s, mods));
-    } else if (use_stream) {
-        // the streaming kernel (ajx_stream.h; ablate 50: its structural pass alone, 51: no
-        // fold), its stage B over the d_perm buffer as the stage-B list
-        w->rows_stride = rows_stride;
-        HIP_OK(ajx::launch_eval_stream(w->d_sets, d_set_of_req, (uint32_t)max_blob, max_rec, d_arena,
-                                       d_offs, d_lens, n, d_out_tristate, d_out_err_idx, d_out_bitmap,
-                                       bitmap_stride_words, w->d_rows, rows_stride, keep_rows, w->d_perm, w->d_slow,
-                                       w->d_slow + 3, s, ablate == 50 ? 1 : ablate == 51 ? 2 : ablate == 53 ? 3 : 0, mods,
-                                       per, &cnt_zero));
+    const ajx::Batch batch{w->d_sets, d_set_of_req, d_arena, d_offs, d_lens, n};
+    const ajx::Results res{d_out_tristate, d_out_err_idx, d_out_bitmap, bitmap_stride_words};
+    if (plan.path == ajx::kPathExact) {
+        HIP_OK(ajx::launch_eval_scan(batch, res, plan.mods != 0, s));
+    } else if (plan.path == ajx::kPathStream) {
+        // the streaming kernel (ajx_stream.h), its stage B over the d_perm buffer as the
+        // stage-B list; the slow ids after its three counters
+        const ajx::Work work{w->d_rows, plan.rows_stride, w->d_slow, w->d_slow + 3};
+        HIP_OK(ajx::launch_eval_stream(batch, res, work, plan, in.max_blob, in.max_rec, w->d_perm, &cnt_zero, s));
         w->cnt_zero = w->exact3 = cnt_zero;
     } else {
-        // length-bucketed order: one ruleset for the batch (multi-tenant batches keep the
-        // caller's bucketing by AuthConfig), a full kernel, batches worth sorting
         const uint32_t* perm = nullptr;
         uint32_t* pos_of = nullptr;
-        const uint32_t n_out = n_sets == 1 && h0->pad1[0] ? h0->pad1[0] : 1u;
-        if (len_sort && (n_sets == 1 || len_sort > 1) && full && n >= 4096) {
-            // (one ruleset: its outputs in work-item order, gathered back by pos_of)
-            // (forests, several results per request, keep writing at the request: the
-            // gather's strided byte copies cost more than the scattered stores, c5 12.0 → 12.4 ms)
-            if (n_sets == 1 && n_out == 1) {
-                rc = ensure_tout(w, ajx::tout_bytes(n, n_out, d_out_bitmap ? bitmap_stride_words : 0u));
+        if (plan.len_order) {
+            if (plan.want_pos_of) {
+                rc = ensure_tout(w, ajx::tout_bytes(n, plan.n_out, plan.tout_bm ? bitmap_stride_words : 0u));
                 if (rc != AUTHJX_OK) return rc;
                 pos_of = w->d_perm + (size_t)n + 4096;
             }
-            HIP_OK(ajx::launch_len_order(d_lens, n, w->d_perm + n, w->d_perm, s, pos_of));
+            HIP_OK(ajx::launch_len_order(d_lens, n, w->d_perm + n, w->d_perm, pos_of, s));
             perm = w->d_perm;
         }
         w->rows_perm = perm;
-        // uniform batch: the blob staged once per workgroup; multi-tenant batch: nonzero
-        // turns on the per-workgroup staging of its runs' rulesets (ajx_scan_fused_tenant)
-        const uint32_t stage_bytes =
-            n_sets == 1 ? (max_blob <= ajx::kMaxSharedBlobBytes ? (uint32_t)max_blob : 0u)
-                        : (!no_tenant_stage ? (uint32_t)std::min<size_t>(max_blob, ajx::kMaxTenantStageBytes) : 0u);
-        HIP_OK(ajx::launch_eval_fast(w->d_sets, d_set_of_req, stage_bytes, d_arena, d_offs, d_lens, n,
-                                     d_out_tristate, d_out_err_idx, d_out_bitmap, bitmap_stride_words,
-                                     w->d_rows, row_stride, w->d_slow, w->d_slow + 1, s,
-                                     ablate < 20 ? ablate : 0, perm, mods, keep_rows, n_sets == 1 ? h0->lean_feat : 3u,
-                                     pos_of, pos_of ? w->d_tout : nullptr, n_out));
+        const ajx::Work work{w->d_rows, plan.rows_stride, w->d_slow, w->d_slow + 1};
+        HIP_OK(ajx::launch_eval_fast(batch, res, work, plan, perm, pos_of, pos_of ? w->d_tout : nullptr, s));
     }
     return batch_done(w, sets, n_sets);
 }
@@ -694,15 +657,15 @@ int authjx_select_text_batch_device(authjx_ctx* ctx, const authjx_ruleset* const
     if (!exact && (rc = ensure_work(w, n, row_stride)) != AUTHJX_OK) return rc;
     const uint32_t* perm = nullptr;
     if (!exact && len_sort && n_sets == 1 && n >= 4096) {
-        HIP_OK(ajx::launch_len_order(d_lens, n, w->d_perm + n, w->d_perm, s));
+        HIP_OK(ajx::launch_len_order(d_lens, n, w->d_perm + n, w->d_perm, nullptr, s));
         perm = w->d_perm;
     }
     const uint32_t shared_bytes =
         (n_sets == 1 && sets[0]->c.blob.size() <= ajx::kMaxSharedBlobBytes) ? (uint32_t)sets[0]->c.blob.size() : 0u;
-    HIP_OK(ajx::launch_select(w->d_sets, d_set_of_req, shared_bytes, d_arena, d_offs, d_lens, n,
-                              reinterpret_cast<uint32_t*>(d_out_values), values_stride,
-                              exact ? nullptr : w->d_rows, row_stride, w->d_slow, w->d_slow + 1, perm, d_out_text,
-                              text_stride, s));
+    const ajx::Batch batch{w->d_sets, d_set_of_req, d_arena, d_offs, d_lens, n};
+    const ajx::Values values{reinterpret_cast<uint32_t*>(d_out_values), values_stride, d_out_text, text_stride};
+    const ajx::Work work{exact ? nullptr : w->d_rows, row_stride, w->d_slow, w->d_slow + 1};
+    HIP_OK(ajx::launch_select(batch, shared_bytes, values, work, perm, s));
     return batch_done(w, sets, n_sets);
 }
 
@@ -734,9 +697,10 @@ int authjx_select_from_eval_device(authjx_ctx* ctx, const authjx_ruleset* rs, ui
     const authjx_ruleset* one[1] = {rs};
     int rc = ensure_sets(w, ctx->device, one, 1);
     if (rc != AUTHJX_OK) return rc;
-    HIP_OK(ajx::launch_select_rows(w->d_sets, d_arena, d_offs, d_lens, n, reinterpret_cast<uint32_t*>(d_out_values),
-                                   values_stride, w->d_rows, w->rows_stride, first_pattern, w->rows_perm,
-                                   w->rows_wave, s));
+    const ajx::Batch batch{w->d_sets, nullptr, d_arena, d_offs, d_lens, n};
+    const ajx::Values values{reinterpret_cast<uint32_t*>(d_out_values), values_stride, nullptr, 0};
+    const ajx::Work work{w->d_rows, w->rows_stride, nullptr, nullptr};
+    HIP_OK(ajx::launch_select_rows(batch, values, work, first_pattern, w->rows_perm, w->rows_wave, s));
     return batch_done(w, one, 1);
 }
 
@@ -795,12 +759,14 @@ int authjx_select_text_batch(authjx_ctx* ctx, const authjx_ruleset* const* sets,
     return AUTHJX_OK;
 }
 
-// Profiling only (not in authjx.h): replace stage A by a reduced variant whose outputs
-// are meaningless, to price its parts (loads, classification) on the hardware.
+// Profiling only (not in authjx.h): the kernel mode (ajx::KernelMode, ajx_plan.h) of the
+// context's evaluations; some modes replace stage A by a reduced variant whose outputs are
+// meaningless, to price its parts on the hardware. AUTHJX_EINVAL for a number that names
+// no mode (the retired 1..3 and 10..12 among them); the mode then stays as it was.
 int authjx_debug_ablate(authjx_ctx* ctx, int mode) {
-    if (!ctx) return AUTHJX_EINVAL;
+    if (!ctx || !ajx::mode_known(mode)) return AUTHJX_EINVAL;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->ablate = mode;
+    ctx->mode = mode;
     return AUTHJX_OK;
 }
 

@@ -472,7 +472,6 @@ struct Scan {
 
     // process the 64 document bytes of window `blk` (ring position of byte 0 = a, a
     // multiple of 64; doc position of byte 0 = bp)
-    template <int MODE = 0>
     AJX_HD void window(const Block16* blk, uint32_t a, int32_t bp) {
         wa = a;
         bpos = bp;
@@ -539,10 +538,6 @@ struct Scan {
         carry_oq = last_oq;
         if (oq) last_oq = (uint32_t)(bp + (int32_t)hibit64f(oq));
         uint64_t toks = (mst & outside) | (qu & ~instr);
-        if constexpr (MODE == 2) {  // ablation: classification only
-            gap_cnt += popc64f(toks) + popc64f(ns);
-            return;
-        }
         uint64_t below = 0;  // bits already consumed
         while (toks) {
             const uint32_t i = ctz64f(toks);
@@ -610,8 +605,7 @@ AJX_HD Tables blob_tables(const uint8_t* blob) {
 // Stage A for one request. `row` = capture row (1 + n_selectors u64); `ring` = the
 // work-item's window ring (128 B). Returns true when the row is valid (false: the
 // request needs the exact scan).
-// MODE (profiling ablations only): 0 = full scan, 1 = loads only, 2 = loads + classification
-template <int MODE = 0, class LoadBlock>
+template <class LoadBlock>
 AJX_HD bool scan_doc(const uint8_t* blob, const Tables& tab, const uint8_t* d, uint32_t n, RowRef row,
                      const WinRing& ring, LoadBlock load) {
     const RulesetHdr* h = (const RulesetHdr*)blob;
@@ -655,21 +649,13 @@ AJX_HD bool scan_doc(const uint8_t* blob, const Tables& tab, const uint8_t* d, u
 #pragma unroll
     for (int j = 0; j < 4; j++) nxt[j] = load((uint32_t)(4 + j), nblk);
     for (uint32_t b0 = 0; b0 < nblk; b0 += 4) {
-        if constexpr (MODE == 1) {
-            s.found ^= (uint64_t)(cur[0].x ^ cur[1].y ^ cur[2].z ^ cur[3].w) << (b0 & 31);
-        } else {
-            s.window<MODE>(cur, b0 * 16, (int32_t)(b0 * 16) - (int32_t)mis);
-        }
+        s.window(cur, b0 * 16, (int32_t)(b0 * 16) - (int32_t)mis);
         if (s.st >= X_DONE) break;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             cur[j] = nxt[j];
             nxt[j] = load(b0 + 8 + (uint32_t)j, nblk);
         }
-    }
-    if constexpr (MODE != 0) {
-        row[0] = s.found + s.gap_cnt;
-        return true;
     }
     if (s.st != X_DONE) {
         row[0] = kRowSlow;

@@ -154,24 +154,39 @@ constexpr uint32_t kWinRingBytesPerWave = 8 * 64 * 16;
 // group (4 waves/SIMD by registers either way)
 constexpr uint32_t kFastBlock = 512;
 constexpr uint32_t kFastMaxBlock = 1024;
-#ifndef AJX_FAST_WAVES
-#define AJX_FAST_WAVES 4  // waves per SIMD the single-pass kernels' register budget is set for
-#endif
-// the workgroup size that fits the most waves per CU for a staged blob of `blob_bytes`
-// (0: nothing staged); the smallest such size on a tie: a workgroup retires as a unit, so
-// smaller ones leave fewer idle waves behind the longest document (measured: c2 4-wave
-// 2.03 ms vs 8-wave 2.11; c3 at 16 waves/CU 2 x 8-wave 3.78 vs 1 x 16-wave 4.03)
-static uint32_t fast_block(uint32_t blob_bytes) {
-    const uint32_t stage = (blob_bytes + 15u) & ~15u;
+// dynamic LDS of the single-pass kernels: [blob copy (staged_bytes, 0: none)] [one window
+// ring per wave of the workgroup]
+struct RingGeom {
+    uint32_t ring_off;  // the rings' offset: the blob copy's size, 16-byte aligned
+    uint32_t lds;       // dynamic LDS bytes of the workgroup
+};
+static inline RingGeom ring_geom(uint32_t staged_bytes, uint32_t block, uint32_t ring_bytes = kWinRingBytesPerWave) {
+    const uint32_t ring_off = (staged_bytes + 15u) & ~15u;
+    return RingGeom{ring_off, ring_off + (block / 64) * ring_bytes};
+}
+// the workgroup size, 256 .. max_block, that fits the most waves per CU (at most `waves`
+// per SIMD, the kernel's register budget) for a staged blob of `blob_bytes` (0: nothing
+// staged) next to rings of `ring_bytes` per wave; the smallest such size on a tie: a
+// workgroup retires as a unit, so smaller ones leave fewer idle waves behind the longest
+// document (measured: c2 4-wave 2.03 ms vs 8-wave 2.11; c3 at 16 waves/CU 2 x 8-wave 3.78
+// vs 1 x 16-wave 4.03)
+static inline uint32_t staged_block(uint32_t blob_bytes, uint32_t max_block, uint32_t waves, uint32_t ring_bytes) {
     uint32_t best = 0, best_w = 0;
-    for (uint32_t b = 256; b <= kFastMaxBlock; b *= 2) {
-        const uint32_t lds = stage + (b / 64) * kWinRingBytesPerWave;
+    for (uint32_t b = 256; b <= max_block; b *= 2) {
+        const uint32_t lds = ring_geom(blob_bytes, b, ring_bytes).lds;
         uint32_t w = lds <= 160u * 1024u ? (160u * 1024u / lds) * (b / 64) : 0u;
-        if (w > 4u * AJX_FAST_WAVES) w = 4u * AJX_FAST_WAVES;
+        if (w > 4u * waves) w = 4u * waves;
         if (w > best_w) best = b, best_w = w;
     }
     return best ? best : 256u;
 }
+// (the token scanner's kernels)
+static inline uint32_t fast_block(uint32_t blob_bytes) {
+    return staged_block(blob_bytes, kFastMaxBlock, AJX_FAST_WAVES, kWinRingBytesPerWave);
+}
+// keep_rows (the stream and lean kernels' parameter), bit 0: every request's capture row is
+// written, for authjx_select_from_eval_device. Each kernel names its own bit 1.
+constexpr uint32_t kKeepRows = 1u;
 __device__ __forceinline__ WinRing lane_ring(uint32_t ring_off) {
     extern __shared__ uint4 s_dyn_ring[];
     WinRing r;
@@ -182,7 +197,6 @@ __device__ __forceinline__ WinRing lane_ring(uint32_t ring_off) {
 }
 
 // stage A for request r: single-pass scan into its capture row (false: slow list)
-template <int MODE>
 __device__ __forceinline__ bool scan_request(const uint8_t* blob, const uint8_t* d, uint32_t len, RowRef row,
                                              const WinRing& ring) {
     const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
@@ -198,7 +212,7 @@ __device__ __forceinline__ bool scan_request(const uint8_t* blob, const uint8_t*
         }
         return Block16{0u, 0u, 0u, 0u};
     };
-    return scan_doc<MODE>(blob, blob_tables(blob), d, len, row, ring, load);
+    return scan_doc(blob, blob_tables(blob), d, len, row, ring, load);
 }
 
 }  // namespace ajx

@@ -1,14 +1,21 @@
-// ajx_kernels.hip — gfx950 kernels of the batched evaluator.
+// ajx_kernels.hip — the gfx950 kernels of the batched evaluator, except the lean and
+// multi-tenant single-pass kernels (ajx_lean.hip), and the launchers of every path.
 //
-// ajx_scan_fast  stage A, one work-item per request: single pass over the document,
-//                all selectors followed at once through the ruleset trie; writes each
-//                selector's value span to the request's capture row (ajx_fast.h).
-//                Requests it can not prove gjson-equivalent go to a slow list.
-// ajx_patterns   stage B, one work-item per request: patterns on the captured values,
-//                T bitmap, And/Or fold.
-// ajx_eval_scan  one work-item per request on the slow list (or on every request when
-//                forced): for each selector an exact gjson.Get scan (ajx_device.h gj_get),
-//                then the patterns and the fold. Exact for arbitrary input bytes.
+//   ajx_eval_scan<MODS>       the exact scan (ajx_device.h gj_get; exact for arbitrary bytes):
+//                             per selector an exact gjson.Get scan, the patterns, the fold
+//   ajx_eval_scan_list<MODS>  the same over the slow list a faster kernel left
+//   ajx_scan_fast<SHARED>     the token scanner (ajx_fast.h), stage A alone: every selector's
+//                             value span into the request's capture row (launch_select)
+//   ajx_scan_fused            its stage A then stage B, tables from global memory
+//                             (multi-tenant batches without staging)
+//   ajx_scan_stream<MODE, MT, LAT, FIN>  the streaming kernel (ajx_stream.h), a span of
+//                             requests per wave: the walk, the eager fold; FIN: the stage-B list
+//   ajx_stream_finish<MT, EXACT>  its stage B over the stage-B list
+//   ajx_len_hist, ajx_len_scan, ajx_len_scatter  large batches' counting sort by length class
+//   ajx_unpermute             work-item-ordered outputs back to request order
+//   ajx_select_values<TEXT>   gjson.Get per pattern selector, from capture rows or exact
+// Launchers: launch_eval_scan, launch_eval_stream, launch_eval_fast (the single-pass paths
+// of an EvalPlan, ajx_plan.h), launch_len_order, launch_select, launch_select_rows.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -157,24 +164,15 @@ __global__ __launch_bounds__(256) void ajx_eval_scan_list(const uint8_t* const* 
 
 // the exact scan over the slow list; the instance with modifier buffers when the batch's
 // rulesets have modifier chains
-static void launch_slow_list(bool mods, uint32_t sgrid, hipStream_t stream, const uint8_t* const* d_sets,
-                             const uint32_t* d_set_of_req, const uint8_t* d_arena, const uint64_t* d_offs,
-                             const uint32_t* d_lens, const uint32_t* d_slow_count, const uint32_t* d_slow_ids,
-                             uint8_t* d_tri, int32_t* d_err, uint64_t* d_bm, uint32_t stride) {
-    if (mods)
-        hipLaunchKernelGGL(ajx_eval_scan_list<true>, dim3(sgrid), dim3(256), 0, stream, d_sets, d_set_of_req, d_arena,
-                           d_offs, d_lens, d_slow_count, d_slow_ids, d_tri, d_err, d_bm, stride);
-    else
-        hipLaunchKernelGGL(ajx_eval_scan_list<false>, dim3(sgrid), dim3(256), 0, stream, d_sets, d_set_of_req, d_arena,
-                           d_offs, d_lens, d_slow_count, d_slow_ids, d_tri, d_err, d_bm, stride);
+static void launch_slow_list(const Batch& b, const Results& res, const Work& work, bool mods, uint32_t sgrid,
+                             hipStream_t stream) {
+    hipLaunchKernelGGL((mods ? ajx_eval_scan_list<true> : ajx_eval_scan_list<false>), dim3(sgrid), dim3(256), 0, stream,
+                       b.sets, b.set_of_req, b.arena, b.offs, b.lens, work.slow_count, work.slow_ids, res.tri, res.err,
+                       res.bm, res.stride);
 }
 
-
-
-
-// Stage A alone (profiling split / ablations): structural scan -> capture rows.
-// MODE 1/2 are the loads-only / loads+classification ablations.
-template <int MODE, bool SHARED>
+// Stage A alone (launch_select): structural scan -> capture rows.
+template <bool SHARED>
 __global__ __launch_bounds__(kFastMaxBlock, AJX_FAST_WAVES) void ajx_scan_fast(const uint8_t* const* __restrict__ sets,
                                                      const uint32_t* __restrict__ set_of_req,
                                                      const uint8_t* __restrict__ arena,
@@ -188,25 +186,8 @@ __global__ __launch_bounds__(kFastMaxBlock, AJX_FAST_WAVES) void ajx_scan_fast(c
     const uint32_t r = k < n ? (perm ? perm[k] : k) : 0u;
     const uint8_t* blob = stage_blob<SHARED>(sets[SHARED || !set_of_req ? 0 : set_of_req[r]]);
     if (k >= n) return;
-    if (!scan_request<MODE>(blob, arena + offs[r], lens[r], rows + (size_t)r * row_stride, lane_ring(ring_off)))
+    if (!scan_request(blob, arena + offs[r], lens[r], rows + (size_t)r * row_stride, lane_ring(ring_off)))
         slow_ids[atomicAdd(slow_count, 1u)] = r;
-}
-
-// Stage B alone (profiling split): patterns on the captured values, bitmap, fold
-template <bool SHARED>
-__global__ __launch_bounds__(kFastMaxBlock) void ajx_patterns(const uint8_t* const* __restrict__ sets,
-                                                    const uint32_t* __restrict__ set_of_req,
-                                                    const uint8_t* __restrict__ arena,
-                                                    const uint64_t* __restrict__ offs, uint32_t n,
-                                                    const uint64_t* __restrict__ rows, uint32_t row_stride,
-                                                    uint8_t* __restrict__ out_tri, int32_t* __restrict__ out_err,
-                                                    uint64_t* __restrict__ out_bm, uint32_t stride) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint8_t* blob = stage_blob<SHARED>(sets[SHARED || !set_of_req ? 0 : (r < n ? set_of_req[r] : 0)]);
-    if (r >= n) return;
-    const uint64_t* row = rows + (size_t)r * row_stride;
-    if (row[0] & kRowSlow) return;
-    (void)finish_request(r, blob, arena + offs[r], row, out_tri, out_err, out_bm, stride);  // (profiling split)
 }
 
 // The token-scanner single-pass kernel for multi-tenant batches without staging: stage A
@@ -231,7 +212,7 @@ __global__ __launch_bounds__(kFastMaxBlock, AJX_FAST_WAVES) void ajx_scan_fused(
     if (k >= n) return;
     const RowRef row = wave_row(rows, row_stride, k);
     const uint8_t* d = arena + offs[r];
-    if (!scan_request<0>(blob, d, lens[r], row, lane_ring(ring_off))) {
+    if (!scan_request(blob, d, lens[r], row, lane_ring(ring_off))) {
         slow_ids[atomicAdd(slow_count, 1u)] = r;
         return;
     }
@@ -241,10 +222,10 @@ __global__ __launch_bounds__(kFastMaxBlock, AJX_FAST_WAVES) void ajx_scan_fused(
     }
 }
 
-
-
 // a stage-B list entry the stream could not prove (merge_slow): the exact scan decides it
 constexpr uint32_t kStageExact = 1u << 31;
+// keep_rows bit 1 (bit 0: kKeepRows), profiling: the phase clocks of a one-request wave
+constexpr uint32_t kKeepTiming = 2u;
 
 // The streaming kernel (ajx_stream.h): each wave takes a span of stream::kSpan requests in
 // arena order and reads their bytes as one coalesced stream; a lane per request then folds
@@ -279,8 +260,8 @@ __device__ __forceinline__ void stream_body(const uint8_t* const* __restrict__ s
     const uint32_t span = blockIdx.x * (blockDim.x >> 6) + w;
     // (profiling, keep_rows bit 1: lane 0 of a one-request wave writes its phases' clock
     // counts over the request's bitmap word: blob copy | stream | stage B, 21 bits each, x16)
-    const bool timing = (keep_rows & 2u) != 0;
-    keep_rows &= 1u;
+    const bool timing = (keep_rows & kKeepTiming) != 0;
+    keep_rows &= kKeepRows;
     const uint64_t c0 = timing ? __builtin_readcyclecounter() : 0ull;
     uint64_t c1 = 0, c2 = 0;
     const uint8_t* blob;
@@ -517,6 +498,7 @@ uint32_t stream_records(const uint8_t* host_blob) {
 }
 
 static_assert(kStreamSpan == stream::kSpan, "requests per wave");
+static_assert(kStreamStructural == 1 && kStreamNoFold == 2, "the streaming kernel's MODE");
 
 // 4-wave workgroups (the kernel's launch bounds), each with its own blob copy
 constexpr uint32_t kStreamBlock = 256;
@@ -524,19 +506,19 @@ constexpr uint32_t kStreamBlock = 256;
 // entries per lane
 constexpr uint32_t kFinMaxN = 512;
 
-hipError_t launch_eval_stream(const uint8_t* const* d_sets, const uint32_t* d_set_of_req, uint32_t blob_bytes,
-                              uint32_t n_rec, const uint8_t* d_arena, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
-                              uint8_t* d_tri, int32_t* d_err, uint64_t* d_bm, uint32_t stride, uint64_t* d_rows,
-                              uint32_t row_stride, bool keep_rows, uint32_t* d_stage_ids, uint32_t* d_slow_count,
-                              uint32_t* d_slow_ids, hipStream_t stream, int mode, bool mods, uint32_t per,
-                              bool* counters_zero) {
+hipError_t launch_eval_stream(const Batch& b, const Results& res, const Work& work, const EvalPlan& plan,
+                              uint32_t blob_bytes, uint32_t n_rec, uint32_t* d_stage_ids, bool* counters_zero,
+                              hipStream_t stream) {
     const bool was_zero = counters_zero && *counters_zero;
     if (counters_zero) *counters_zero = false;
+    const uint32_t n = b.n;
     if (n == 0) return hipSuccess;
-    if (row_stride < 5u + n_rec) return hipErrorInvalidValue;
-    const bool mt = d_set_of_req != nullptr;
-    const bool timing = mode == 3;  // (profiling: the LAT instance's phase clocks, §ajx_scan_stream)
-    if (timing) mode = 0;
+    if (work.row_stride < 5u + n_rec) return hipErrorInvalidValue;
+    const bool mt = b.set_of_req != nullptr;
+    const bool timing = plan.stream_mode == kStreamTiming;  // (profiling: the LAT instance's phase clocks)
+    const int mode = timing ? 0 : (int)plan.stream_mode;  // (the kernel's MODE: 1 structural pass alone, 2 no fold)
+    const bool keep_rows = plan.keep_rows != 0, mods = plan.mods != 0;
+    uint32_t per = plan.per;
     if (mt) {
         if (mode != 0) return hipErrorInvalidValue;
         per = 1;
@@ -565,7 +547,7 @@ hipError_t launch_eval_stream(const uint8_t* const* d_sets, const uint32_t* d_se
     // (one fill: the slow count, the stage-B count and the finished-wave count after it;
     // none after a FIN launch on this stream, whose last wave cleared them)
     hipError_t e = hipSuccess;
-    if (!was_zero && (e = hipMemsetAsync(d_slow_count, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    if (!was_zero && (e = hipMemsetAsync(work.slow_count, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
     static std::atomic<uint64_t> attr_done{0};
     e = attr_once(attr_done, [] {
         for (const void* k : {reinterpret_cast<const void*>(&ajx_scan_stream<0>),
@@ -593,12 +575,11 @@ hipError_t launch_eval_stream(const uint8_t* const* d_sets, const uint32_t* d_se
         return hipSuccess;
     });
     if (e != hipSuccess) return e;
-#define AJX_STREAM_LAUNCH(M, T, LT, F)                                                                        \
-    hipLaunchKernelGGL((ajx_scan_stream<M, T, LT, F>), dim3(grid), dim3(block), lds, stream, d_sets, d_set_of_req,  \
-                       d_arena, \
-                       d_offs, d_lens, n, \
-                       d_slow_count, d_slow_ids, d_stage_ids, d_tri, d_err, d_bm, stride, wave_off, wave_bytes,       \
-                       d_rows, row_stride, (keep_rows ? 1u : 0u) | (timing ? 2u : 0u), per, merge ? 1u : 0u)
+#define AJX_STREAM_LAUNCH(M, T, LT, F)                                                                           \
+    hipLaunchKernelGGL((ajx_scan_stream<M, T, LT, F>), dim3(grid), dim3(block), lds, stream, b.sets, b.set_of_req, \
+                       b.arena, b.offs, b.lens, n, work.slow_count, work.slow_ids, d_stage_ids, res.tri, res.err,  \
+                       res.bm, res.stride, wave_off, wave_bytes, work.rows, work.row_stride,                        \
+                       (keep_rows ? kKeepRows : 0u) | (timing ? kKeepTiming : 0u), per, merge ? 1u : 0u)
     const bool lat = merge && !keep_rows;
     // (stage B and the exact scan in the last wave: no second launch). Only for batches of at
     // most kFinMaxN requests: that wave walks the list 64 entries at a time, so a large batch
@@ -628,10 +609,10 @@ hipError_t launch_eval_stream(const uint8_t* const* d_sets, const uint32_t* d_se
     if (mode != 0 || fin) return hipSuccess;
     // stage B and the exact scan over their lists (grid-stride: the lists' lengths are on the device)
     const uint32_t fgrid = n < 2048u * 256u ? (n + 255) / 256 : 4096;
-#define AJX_FINISH_LAUNCH(T, X, LDS)                                                                              \
-    hipLaunchKernelGGL((ajx_stream_finish<T, X>), dim3(fgrid), dim3(256), LDS, stream, d_sets,                    \
-                       T ? d_set_of_req : nullptr, d_arena, d_offs, d_lens, d_stage_ids, d_rows, row_stride,      \
-                       d_slow_count, d_slow_ids, d_tri, d_err, d_bm, stride)
+#define AJX_FINISH_LAUNCH(T, X, LDS)                                                                            \
+    hipLaunchKernelGGL((ajx_stream_finish<T, X>), dim3(fgrid), dim3(256), LDS, stream, b.sets,                     \
+                       T ? b.set_of_req : nullptr, b.arena, b.offs, b.lens, d_stage_ids, work.rows,                \
+                       work.row_stride, work.slow_count, work.slow_ids, res.tri, res.err, res.bm, res.stride)
     if (mt && mods)
         AJX_FINISH_LAUNCH(true, 2, 0);
     else if (mt)
@@ -646,8 +627,7 @@ hipError_t launch_eval_stream(const uint8_t* const* d_sets, const uint32_t* d_se
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (merge) return hipSuccess;
     const uint32_t sgrid = n < 1024u * 128u ? 2 * ((n + 255) / 256) : 4096;
-    launch_slow_list(mods, sgrid, stream, d_sets, d_set_of_req, d_arena, d_offs, d_lens, d_slow_count, d_slow_ids, d_tri,
-                     d_err, d_bm, stride);
+    launch_slow_list(b, res, work, mods, sgrid, stream);
     return hipGetLastError();
 }
 
@@ -763,7 +743,7 @@ __global__ __launch_bounds__(256) void ajx_unpermute(const uint32_t* __restrict_
 }
 
 hipError_t launch_len_order(const uint32_t* d_lens, uint32_t n, uint32_t* d_hist, uint32_t* d_perm,
-                            hipStream_t stream, uint32_t* d_pos_of) {
+                            uint32_t* d_pos_of, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(d_hist, 0, (2 * kLenBuckets + 1) * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     const uint32_t blocks = (n + kLenBuckets - 1) / kLenBuckets;
@@ -863,24 +843,21 @@ __global__ __launch_bounds__(256) void ajx_select_values(const uint8_t* const* _
     }
 }
 
-hipError_t launch_select(const uint8_t* const* d_sets, const uint32_t* d_set_of_req, uint32_t shared_blob_bytes,
-                         const uint8_t* d_arena, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
-                         uint32_t* d_out, uint32_t stride, uint64_t* d_rows, uint32_t row_stride,
-                         uint32_t* d_slow_count, uint32_t* d_slow_ids, const uint32_t* d_perm, uint8_t* d_text,
-                         uint32_t text_stride, hipStream_t stream) {
+hipError_t launch_select(const Batch& b, uint32_t shared_blob_bytes, const Values& v, const Work& work,
+                         const uint32_t* d_perm, hipStream_t stream) {
+    const uint32_t n = b.n;
     if (n == 0) return hipSuccess;
-    if (d_rows) {  // stage A of the single-pass kernel captures every selector's span
-        const bool shared = shared_blob_bytes != 0 && d_set_of_req == nullptr;
+    if (work.rows) {  // stage A of the single-pass kernel captures every selector's span
+        const bool shared = shared_blob_bytes != 0 && b.set_of_req == nullptr;
         const uint32_t fblock = shared ? fast_block(shared_blob_bytes) : kFastBlock;
         const uint32_t fgrid = (n + fblock - 1) / fblock;
-        const uint32_t ring_off = shared ? (shared_blob_bytes + 15u) & ~15u : 0u;
-        const uint32_t lds = ring_off + (fblock / 64) * kWinRingBytesPerWave;
-        hipError_t e = hipMemsetAsync(d_slow_count, 0, sizeof(uint32_t), stream);
+        const RingGeom g = ring_geom(shared ? shared_blob_bytes : 0u, fblock);
+        hipError_t e = hipMemsetAsync(work.slow_count, 0, sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;
         static std::atomic<uint64_t> attr_done{0};
         e = attr_once(attr_done, [] {
-            const void* ks[] = {reinterpret_cast<const void*>(&ajx_scan_fast<0, true>),
-                                reinterpret_cast<const void*>(&ajx_scan_fast<0, false>)};
+            const void* ks[] = {reinterpret_cast<const void*>(&ajx_scan_fast<true>),
+                                reinterpret_cast<const void*>(&ajx_scan_fast<false>)};
             for (const void* k : ks) {
                 const hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 if (r != hipSuccess) return r;
@@ -888,155 +865,89 @@ hipError_t launch_select(const uint8_t* const* d_sets, const uint32_t* d_set_of_
             return hipSuccess;
         });
         if (e != hipSuccess) return e;
-        if (shared)
-            hipLaunchKernelGGL((ajx_scan_fast<0, true>), dim3(fgrid), dim3(fblock), lds, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids, ring_off,
-                               d_perm);
-        else
-            hipLaunchKernelGGL((ajx_scan_fast<0, false>), dim3(fgrid), dim3(fblock), lds, stream, d_sets,
-                               d_set_of_req, d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids,
-                               ring_off, d_perm);
+        hipLaunchKernelGGL((shared ? ajx_scan_fast<true> : ajx_scan_fast<false>), dim3(fgrid), dim3(fblock), g.lds,
+                           stream, b.sets, b.set_of_req, b.arena, b.offs, b.lens, n, work.rows, work.row_stride,
+                           work.slow_count, work.slow_ids, g.ring_off, d_perm);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const uint32_t block = 256;
     const uint32_t grid = (n + block - 1) / block;
-    if (d_text)
-        hipLaunchKernelGGL(ajx_select_values<true>, dim3(grid), dim3(block), 0, stream, d_sets, d_set_of_req, d_arena,
-                           d_offs, d_lens, n, d_out, stride, d_rows, row_stride, 0u, nullptr, 0u, d_text, text_stride);
-    else
-        hipLaunchKernelGGL(ajx_select_values<false>, dim3(grid), dim3(block), 0, stream, d_sets, d_set_of_req, d_arena,
-                           d_offs, d_lens, n, d_out, stride, d_rows, row_stride, 0u, nullptr, 0u, nullptr, 0u);
+    hipLaunchKernelGGL((v.text ? ajx_select_values<true> : ajx_select_values<false>), dim3(grid), dim3(block), 0, stream,
+                       b.sets, b.set_of_req, b.arena, b.offs, b.lens, n, v.out, v.stride, work.rows, work.row_stride, 0u,
+                       nullptr, 0u, v.text, v.text ? v.text_stride : 0u);
     return hipGetLastError();
 }
 
-hipError_t launch_select_rows(const uint8_t* const* d_sets, const uint8_t* d_arena, const uint64_t* d_offs,
-                              const uint32_t* d_lens, uint32_t n, uint32_t* d_out, uint32_t stride,
-                              const uint64_t* d_rows, uint32_t row_stride, uint32_t p0, const uint32_t* d_perm,
+hipError_t launch_select_rows(const Batch& b, const Values& v, const Work& work, uint32_t p0, const uint32_t* d_perm,
                               bool wave_rows, hipStream_t stream) {
-    if (n == 0) return hipSuccess;
+    if (b.n == 0) return hipSuccess;
     const uint32_t block = 256;
-    const uint32_t grid = (n + block - 1) / block;
-    hipLaunchKernelGGL(ajx_select_values<false>, dim3(grid), dim3(block), 0, stream, d_sets, nullptr, d_arena, d_offs,
-                       d_lens, n, d_out, stride, d_rows, row_stride, p0, d_perm, wave_rows ? 1u : 0u, nullptr, 0u);
+    const uint32_t grid = (b.n + block - 1) / block;
+    hipLaunchKernelGGL(ajx_select_values<false>, dim3(grid), dim3(block), 0, stream, b.sets, nullptr, b.arena, b.offs,
+                       b.lens, b.n, v.out, v.stride, work.rows, work.row_stride, p0, d_perm, wave_rows ? 1u : 0u,
+                       nullptr, 0u);
     return hipGetLastError();
 }
 
-hipError_t launch_eval_scan(const uint8_t* const* d_sets, const uint32_t* d_set_of_req, const uint8_t* d_arena,
-                            const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint8_t* d_tri,
-                            int32_t* d_err, uint64_t* d_bm, uint32_t stride, hipStream_t stream, bool mods) {
-    if (n == 0) return hipSuccess;
+hipError_t launch_eval_scan(const Batch& b, const Results& res, bool mods, hipStream_t stream) {
+    if (b.n == 0) return hipSuccess;
     const uint32_t block = 256;
-    const uint32_t grid = (n + block - 1) / block;
-    if (mods)
-        hipLaunchKernelGGL(ajx_eval_scan<true>, dim3(grid), dim3(block), 0, stream, d_sets, d_set_of_req, d_arena,
-                           d_offs, d_lens, n, d_tri, d_err, d_bm, stride);
-    else
-        hipLaunchKernelGGL(ajx_eval_scan<false>, dim3(grid), dim3(block), 0, stream, d_sets, d_set_of_req, d_arena,
-                           d_offs, d_lens, n, d_tri, d_err, d_bm, stride);
+    const uint32_t grid = (b.n + block - 1) / block;
+    hipLaunchKernelGGL((mods ? ajx_eval_scan<true> : ajx_eval_scan<false>), dim3(grid), dim3(block), 0, stream, b.sets,
+                       b.set_of_req, b.arena, b.offs, b.lens, b.n, res.tri, res.err, res.bm, res.stride);
     return hipGetLastError();
 }
 
-hipError_t launch_eval_fast(const uint8_t* const* d_sets, const uint32_t* d_set_of_req, uint32_t shared_blob_bytes,
-                            const uint8_t* d_arena, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
-                            uint8_t* d_tri, int32_t* d_err, uint64_t* d_bm, uint32_t stride, uint64_t* d_rows,
-                            uint32_t row_stride, uint32_t* d_slow_count, uint32_t* d_slow_ids, hipStream_t stream,
-                            int mode, const uint32_t* d_perm, bool mods, bool keep_rows, uint32_t lean_feat,
-                            const uint32_t* d_pos_of, uint8_t* d_tout, uint32_t n_out) {
+hipError_t launch_eval_fast(const Batch& b, const Results& res, const Work& work, const EvalPlan& plan,
+                            const uint32_t* d_perm, const uint32_t* d_pos_of, uint8_t* d_tout, hipStream_t stream) {
+    const uint32_t n = b.n;
     if (n == 0) return hipSuccess;
-    const bool shared = shared_blob_bytes != 0 && d_set_of_req == nullptr;
-    // workgroup size by the waves a CU holds (each workgroup stages its own blob copy)
-    uint32_t block = shared ? fast_block(shared_blob_bytes) : kFastBlock;
-    if (mode >= 10 && mode <= 12) {  // profiling: the default kernel at a forced workgroup size
-        block = 256u << (mode - 10);
-        mode = 0;
-        if (((shared ? (shared_blob_bytes + 15u) & ~15u : 0u) + (block / 64) * kWinRingBytesPerWave) > 160u * 1024u)
-            return hipErrorInvalidValue;
-    }
+    if (plan.path != kPathLean && plan.path != kPathTenant && plan.path != kPathFused) return hipErrorInvalidValue;
+    // (the exact scan's grid follows the token scanner's workgroup size for the staged blob)
+    const uint32_t block = plan.path == kPathLean && plan.stage_bytes ? fast_block(plan.stage_bytes) : kFastBlock;
     const uint32_t grid = (n + block - 1) / block;
-    // dynamic LDS of the single-pass kernels: [blob copy (shared)] [window rings]
-    const uint32_t ring_off = shared ? (shared_blob_bytes + 15u) & ~15u : 0u;
-    const uint32_t lds = ring_off + (block / 64) * kWinRingBytesPerWave;
-    hipError_t e = hipMemsetAsync(d_slow_count, 0, sizeof(uint32_t), stream);
+    hipError_t e = hipMemsetAsync(work.slow_count, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    static std::atomic<uint64_t> attr_done{0};
-    e = attr_once(attr_done, [] {
-        const void* ks[] = {reinterpret_cast<const void*>(&ajx_scan_fast<0, true>),
-                            reinterpret_cast<const void*>(&ajx_scan_fast<0, false>),
-                            reinterpret_cast<const void*>(&ajx_scan_fast<1, true>),
-                            reinterpret_cast<const void*>(&ajx_scan_fast<2, true>),
-                            reinterpret_cast<const void*>(&ajx_scan_fused)};
-        for (const void* k : ks) {
-            const hipError_t r = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (r != hipSuccess) return r;
-        }
-        return hipSuccess;
-    });
-    if (e != hipSuccess) return e;
-    if (mode == 1 || mode == 2) {  // profiling ablations of stage A (uniform ruleset only)
-        if (!shared) return hipErrorInvalidValue;
-        if (mode == 1)
-            hipLaunchKernelGGL((ajx_scan_fast<1, true>), dim3(grid), dim3(block), lds, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids, ring_off, nullptr);
-        else
-            hipLaunchKernelGGL((ajx_scan_fast<2, true>), dim3(grid), dim3(block), lds, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids, ring_off, nullptr);
-        return hipGetLastError();
-    }
-    if (mode == 3) {  // profiling split: stage A and stage B as two launches
-        if (shared) {
-            hipLaunchKernelGGL((ajx_scan_fast<0, true>), dim3(grid), dim3(block), lds, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids, ring_off, nullptr);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            hipLaunchKernelGGL((ajx_patterns<true>), dim3(grid), dim3(block), ring_off, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, n, d_rows, row_stride, d_tri, d_err, d_bm, stride);
-        } else {
-            hipLaunchKernelGGL((ajx_scan_fast<0, false>), dim3(grid), dim3(block), lds, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids, ring_off, nullptr);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-            hipLaunchKernelGGL((ajx_patterns<false>), dim3(grid), dim3(block), 0, stream, d_sets, d_set_of_req,
-                               d_arena, d_offs, n, d_rows, row_stride, d_tri, d_err, d_bm, stride);
-        }
-    } else if ((mode >= 15 && mode <= 18) || !d_set_of_req) {
+    if (plan.path == kPathLean) {
         // the lean single-pass kernel (one ruleset; ajx_lean.hip), or its profiling ablations
         // (multi-tenant batches: the staged tenant scanner below. Measured on c4, the lean
         // scan with per-lane table parameters took 6.39 ms and one pass per ruleset of a
         // wave 7.3-7.8 ms, against 5.38 ms for the tenant kernel's LDS-staged tables)
-        if (mode >= 15 && !shared) return hipErrorInvalidValue;
         // in length order, the outputs go to d_tout in work-item order and are gathered back
         // (ajx_unpermute) before the exact scan writes its requests' own
-        const bool out_k = d_perm && d_pos_of && d_tout && mode < 15;
-        const size_t o_err = ((size_t)n * n_out + 255u) & ~(size_t)255u;
-        const size_t o_bm = o_err + (((size_t)n * n_out * 4u + 255u) & ~(size_t)255u);
-        uint8_t* k_tri = out_k ? d_tout : d_tri;
-        int32_t* k_err = out_k ? (d_err ? reinterpret_cast<int32_t*>(d_tout + o_err) : nullptr) : d_err;
-        uint64_t* k_bm = out_k ? (d_bm ? reinterpret_cast<uint64_t*>(d_tout + o_bm) : nullptr) : d_bm;
-        e = launch_lean(d_sets, shared ? shared_blob_bytes : 0u, d_arena, d_offs, d_lens, n, d_rows, row_stride,
-                        d_slow_count, d_slow_ids, k_tri, k_err, k_bm, stride, stream, mode >= 15 ? mode - 14 : 0,
-                        d_perm, keep_rows, lean_feat, out_k);
-        if (e != hipSuccess || mode >= 15) return e;
+        const bool out_k = plan.out_k != 0;  // (with it come d_perm, d_pos_of and d_tout)
+        const size_t o_err = ((size_t)n * plan.n_out + 255u) & ~(size_t)255u;
+        const size_t o_bm = o_err + (((size_t)n * plan.n_out * 4u + 255u) & ~(size_t)255u);
+        const Results k_res =
+            out_k ? Results{d_tout, res.err ? reinterpret_cast<int32_t*>(d_tout + o_err) : nullptr,
+                            res.bm ? reinterpret_cast<uint64_t*>(d_tout + o_bm) : nullptr, res.stride}
+                  : res;
+        e = launch_lean(b, k_res, work, plan, d_perm, stream);
+        if (e != hipSuccess || plan.abl) return e;
         if (out_k) {
-            hipLaunchKernelGGL(ajx_unpermute, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_pos_of, n, n_out,
-                               stride, k_tri, k_err, k_bm, d_tri, d_err, d_bm);
+            hipLaunchKernelGGL(ajx_unpermute, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_pos_of, n, plan.n_out,
+                               res.stride, k_res.tri, k_res.err, k_res.bm, res.tri, res.err, res.bm);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-    } else if (shared_blob_bytes) {
-        // multi-tenant batch (shared_blob_bytes != 0: staging on): each workgroup stages its
-        // runs' rulesets, those that fit (ajx_scan_fused_tenant);
-        // 4-wave workgroups, so more of them fall inside one AuthConfig's bucket
-        // (staging region: the tenant budget less room for the kernel's static LDS, so
-        // four groups still fit a CU)
-        e = launch_tenant(d_sets, d_set_of_req, d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count,
-                          d_slow_ids, d_tri, d_err, d_bm, stride, stream, d_perm);
-        if (e != hipSuccess) return e;
+    } else if (plan.path == kPathTenant) {
+        // multi-tenant batch, staging on: each workgroup stages its runs' rulesets, those that
+        // fit (ajx_scan_fused_tenant)
+        if ((e = launch_tenant(b, res, work, d_perm, stream)) != hipSuccess) return e;
     } else {
-        hipLaunchKernelGGL(ajx_scan_fused, dim3(grid), dim3(block), lds, stream, d_sets, d_set_of_req,
-                           d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count, d_slow_ids, d_tri, d_err, d_bm,
-                           stride, ring_off, d_perm);
+        static std::atomic<uint64_t> attr_done{0};
+        e = attr_once(attr_done, [] {
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(&ajx_scan_fused),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        });
+        if (e != hipSuccess) return e;
+        const RingGeom g = ring_geom(0u, block);
+        hipLaunchKernelGGL(ajx_scan_fused, dim3(grid), dim3(block), g.lds, stream, b.sets, b.set_of_req, b.arena,
+                           b.offs, b.lens, n, work.rows, work.row_stride, work.slow_count, work.slow_ids, res.tri,
+                           res.err, res.bm, res.stride, g.ring_off, d_perm);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const uint32_t sgrid = grid < 2048 ? 2 * grid : 4096;
-    launch_slow_list(mods, sgrid, stream, d_sets, d_set_of_req, d_arena, d_offs, d_lens, d_slow_count, d_slow_ids,
-                     d_tri, d_err, d_bm, stride);
+    launch_slow_list(b, res, work, plan.mods != 0, sgrid, stream);
     return hipGetLastError();
 }
 

@@ -21,9 +21,9 @@ constexpr uint32_t kLeanMaxBlock = 1024;
 #ifndef AJX_LEAN_WAVES
 #define AJX_LEAN_WAVES AJX_FAST_WAVES  // waves per SIMD the lean kernel's registers are set for
 #endif
-#ifndef AJX_LEAN_MAXBLOCK
-#define AJX_LEAN_MAXBLOCK kLeanMaxBlock
-#endif
+// keep_rows bit 1 (bit 0: kKeepRows): the outputs in work-item order (gathered back by
+// ajx_unpermute)
+constexpr uint32_t kLeanOutByItem = 2u;
 // ABL: profiling ablations (kernel modes 15..18, lean::scan_doc): stage A cut short, no stage B.
 // FEAT: the walker features of the instance (kLeanArr | kLeanCaps). launch_lean picks by the
 // ruleset's kLeanArr alone (RulesetHdr::lean_feat): every instance it launches has kLeanCaps
@@ -37,9 +37,8 @@ __global__ __launch_bounds__(AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES) void ajx_scan_le
     uint32_t keep_rows) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t r = k < n ? (perm ? perm[k] : k) : 0u;
-    // keep_rows bit 1: the outputs in work-item order (gathered back by ajx_unpermute)
-    const uint32_t o = (keep_rows & 2u) ? k : r;
-    keep_rows &= 1u;
+    const uint32_t o = (keep_rows & kLeanOutByItem) ? k : r;
+    keep_rows &= kKeepRows;
     const uint8_t* blob = stage_blob<SHARED>(sets[SHARED || !set_of_req ? 0 : set_of_req[r]]);
     if (k >= n) return;
     extern __shared__ uint4 s_lean_dyn[];
@@ -73,27 +72,13 @@ __global__ __launch_bounds__(AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES) void ajx_scan_le
         slow_ids[atomicAdd(slow_count, 1u)] = r;
     }
 }
-// workgroup size for the lean kernel with a staged blob of `blob_bytes` (as fast_block)
-static uint32_t lean_block(uint32_t blob_bytes) {
-    const uint32_t stage = (blob_bytes + 15u) & ~15u;
-    uint32_t best = 0, best_w = 0;
-    for (uint32_t b = 256; b <= AJX_LEAN_MAXBLOCK; b *= 2) {
-        const uint32_t lds = stage + (b / 64) * lean::kRingBytesPerWave;
-        uint32_t w = lds <= 160u * 1024u ? (160u * 1024u / lds) * (b / 64) : 0u;
-        if (w > 4u * AJX_LEAN_WAVES) w = 4u * AJX_LEAN_WAVES;
-        if (w > best_w) best = b, best_w = w;
-    }
-    return best ? best : 256u;
-}
 
 #define AJX_LEAN_K(SH, A, F) reinterpret_cast<const void*>(&ajx_scan_lean<SH, A, F>)
-hipError_t launch_lean(const uint8_t* const* d_sets, uint32_t shared_blob_bytes, const uint8_t* d_arena,
-                       const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint64_t* d_rows,
-                       uint32_t row_stride, uint32_t* d_slow_count, uint32_t* d_slow_ids, uint8_t* d_tri,
-                       int32_t* d_err, uint64_t* d_bm, uint32_t stride, hipStream_t stream, int abl,
-                       const uint32_t* d_perm, bool keep_rows, uint32_t lean_feat, bool out_k) {
-    if (n == 0) return hipSuccess;
-    const bool shared = shared_blob_bytes != 0;
+hipError_t launch_lean(const Batch& b, const Results& res, const Work& work, const EvalPlan& plan,
+                       const uint32_t* d_perm, hipStream_t stream) {
+    if (b.n == 0) return hipSuccess;
+    const bool shared = plan.stage_bytes != 0;
+    const uint32_t abl = plan.abl;
     static std::atomic<uint64_t> attr_done{0};
     hipError_t e = attr_once(attr_done, [] {
         const void* ks[] = {AJX_LEAN_K(true, 0, 2), AJX_LEAN_K(true, 0, 3), AJX_LEAN_K(false, 0, 3),
@@ -109,17 +94,17 @@ hipError_t launch_lean(const uint8_t* const* d_sets, uint32_t shared_blob_bytes,
         return hipSuccess;
     });
     if (e != hipSuccess) return e;
-    const uint32_t ring_off = shared ? (shared_blob_bytes + 15u) & ~15u : 0u;
-    const uint32_t lblock = shared ? lean_block(shared_blob_bytes) : 256u;
-    const uint32_t lgrid = (n + lblock - 1) / lblock;
-    const uint32_t llds = ring_off + (lblock / 64) * lean::kRingBytesPerWave;
-    const uint32_t keep = (keep_rows ? 1u : 0u) | (out_k && d_perm ? 2u : 0u);
+    const uint32_t lblock =
+        shared ? staged_block(plan.stage_bytes, AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES, lean::kRingBytesPerWave) : 256u;
+    const uint32_t lgrid = (b.n + lblock - 1) / lblock;
+    const RingGeom g = ring_geom(plan.stage_bytes, lblock, lean::kRingBytesPerWave);
+    const uint32_t keep = (plan.keep_rows ? kKeepRows : 0u) | (plan.out_k && d_perm ? kLeanOutByItem : 0u);
     // (two instances, FEAT 2 and 3: without and with array walking, by the ruleset's
     // kLeanArr. Its kLeanCaps bit is not looked at: both instances enter captured containers,
     // whether the ruleset needs that or not. The capture-free instances cost the walk loop
     // scratch reloads of spilled scalar registers, which wait behind the ring's loads in
     // flight: measured slower, c2 1.39 against 1.27 ms)
-    const uint32_t feat = (lean_feat & kLeanArr) ? 3u : 2u;
+    const uint32_t feat = (plan.lean_feat & kLeanArr) ? 3u : 2u;
     using K = void (*)(const uint8_t* const*, const uint32_t*, const uint8_t*, const uint64_t*, const uint32_t*,
                        uint32_t, uint64_t*, uint32_t, uint32_t*, uint32_t*, uint8_t*, int32_t*, uint64_t*, uint32_t,
                        uint32_t, const uint32_t*, uint32_t);
@@ -140,9 +125,9 @@ hipError_t launch_lean(const uint8_t* const* d_sets, uint32_t shared_blob_bytes,
     } else {
         k = feat == 2 ? &ajx_scan_lean<true, 0, 2> : &ajx_scan_lean<true, 0, 3>;
     }
-    hipLaunchKernelGGL(k, dim3(lgrid), dim3(lblock), llds, stream, d_sets, nullptr, d_arena, d_offs, d_lens, n,
-                       d_rows, row_stride, d_slow_count, d_slow_ids, d_tri, d_err, d_bm, stride, ring_off, d_perm,
-                       keep);
+    hipLaunchKernelGGL(k, dim3(lgrid), dim3(lblock), g.lds, stream, b.sets, nullptr, b.arena, b.offs, b.lens, b.n,
+                       work.rows, work.row_stride, work.slow_count, work.slow_ids, res.tri, res.err, res.bm,
+                       res.stride, g.ring_off, d_perm, keep);
     return hipGetLastError();
 }
 #undef AJX_LEAN_K
@@ -240,18 +225,16 @@ __global__ __launch_bounds__(kFastBlock, AJX_FAST_WAVES) void ajx_scan_fused_ten
     // the scanner and of stage B in the kernel, which keeps the lean path's registers)
     const uint8_t* blob = ridx < nst ? reinterpret_cast<const uint8_t*>(s_stage) + my_off : sets[sid];
     if (k >= n) return;
-    if (!scan_request<0>(blob, d, lens[r], row, lane_ring(ring_off)) ||
+    if (!scan_request(blob, d, lens[r], row, lane_ring(ring_off)) ||
         !finish_request(r, blob, d, row, out_tri, out_err, out_bm, stride)) {
         row[0] = kRowSlow;
         slow_ids[atomicAdd(slow_count, 1u)] = r;
     }
 }
 
-hipError_t launch_tenant(const uint8_t* const* d_sets, const uint32_t* d_set_of_req, const uint8_t* d_arena,
-                         const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint64_t* d_rows,
-                         uint32_t row_stride, uint32_t* d_slow_count, uint32_t* d_slow_ids, uint8_t* d_tri,
-                         int32_t* d_err, uint64_t* d_bm, uint32_t stride, hipStream_t stream, const uint32_t* d_perm) {
-    if (n == 0) return hipSuccess;
+hipError_t launch_tenant(const Batch& b, const Results& res, const Work& work, const uint32_t* d_perm,
+                         hipStream_t stream) {
+    if (b.n == 0) return hipSuccess;
     static std::atomic<uint64_t> attr_done{0};
     hipError_t e = attr_once(attr_done, [] {
         // (the kernel also holds static LDS for its run table: ask only for what its launch
@@ -263,11 +246,11 @@ hipError_t launch_tenant(const uint8_t* const* d_sets, const uint32_t* d_set_of_
     if (e != hipSuccess) return e;
     // (staging region: the tenant budget less room for the kernel's static LDS, so two
     // groups still fit a CU)
-    const uint32_t tblock = kTenantBlock, tgrid = (n + tblock - 1) / tblock;
+    const uint32_t tblock = kTenantBlock, tgrid = (b.n + tblock - 1) / tblock;
     const uint32_t toff = kMaxTenantStageBytes - 256u;
     hipLaunchKernelGGL(ajx_scan_fused_tenant, dim3(tgrid), dim3(tblock), toff + (tblock / 64) * kWinRingBytesPerWave,
-                       stream, d_sets, d_set_of_req, d_arena, d_offs, d_lens, n, d_rows, row_stride, d_slow_count,
-                       d_slow_ids, d_tri, d_err, d_bm, stride, toff, d_perm);
+                       stream, b.sets, b.set_of_req, b.arena, b.offs, b.lens, b.n, work.rows, work.row_stride,
+                       work.slow_count, work.slow_ids, res.tri, res.err, res.bm, res.stride, toff, d_perm);
     return hipGetLastError();
 }
 

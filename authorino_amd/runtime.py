@@ -252,7 +252,8 @@ class Context:
         """Select the kernel: 0 the default (the streaming kernel for small batches, the lean
         or multi-tenant kernel otherwise), 41 the lean kernel for every batch, 52 the
         streaming kernel for every one-ruleset batch; 50 / 51 and others are profiling
-        ablations whose outputs are meaningless. Not part of authjx.h."""
+        ablations whose outputs are meaningless (the modes: ajx::KernelMode, csrc/ajx_plan.h).
+        AuthjxError for a number that names no mode. Not part of authjx.h."""
         L = load_library()
         L.authjx_debug_ablate.argtypes = [C.c_void_p, C.c_int]
         _check(L.authjx_debug_ablate(self._h, int(mode)), "authjx_debug_ablate")

@@ -305,3 +305,37 @@ def eval_stream(hr, arena, offs, lens, mode=0, stride=2, dbg=None, per=0):
     if rc < 0:
         return None
     return tri, err, bm, slow
+
+
+class PlanIn(C.Structure):
+    """ajx::PlanIn (csrc/ajx_plan.h): what the choice of kernels reads of a batch."""
+    _fields_ = [(k, C.c_uint32) for k in ("n", "n_sets", "all_stream", "max_rec", "max_sel", "max_blob", "n_trees",
+                                          "lean_feat", "mods", "bitmap")] + \
+               [(k, C.c_int32) for k in ("force_scan", "mode", "len_sort", "no_tenant_stage")] + \
+               [("stream_max_n", C.c_uint32)]
+
+
+PLAN_FIELDS = ("path", "stream_mode", "per", "abl", "keep_rows", "rows_stride", "stage_bytes", "len_order",
+               "want_pos_of", "out_k", "tout_bm", "n_out", "lean_feat", "mods")
+
+
+class EvalPlan(C.Structure):
+    """ajx::EvalPlan: the kernels a batch gets and what they are handed."""
+    _fields_ = [(k, C.c_uint32) for k in PLAN_FIELDS]
+
+
+def plan_eval(**kw) -> dict:
+    """ajx::plan_eval of a PlanIn given by field (others 0): the EvalPlan's fields."""
+    L = lib()
+    L.ht_plan_eval.argtypes = [C.POINTER(PlanIn), C.POINTER(EvalPlan)]
+    L.ht_plan_eval.restype = None
+    out = EvalPlan()
+    L.ht_plan_eval(C.byref(PlanIn(**kw)), C.byref(out))
+    return {k: getattr(out, k) for k in PLAN_FIELDS}
+
+
+def mode_known(mode: int) -> bool:
+    L = lib()
+    L.ht_mode_known.argtypes = [C.c_int]
+    L.ht_mode_known.restype = C.c_int
+    return bool(L.ht_mode_known(int(mode)))

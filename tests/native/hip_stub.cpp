@@ -95,57 +95,48 @@ static void results(uint32_t n, uint8_t* tri, int32_t* err, uint64_t* bm, uint32
     }
 }
 
-hipError_t launch_eval_scan(const uint8_t* const*, const uint32_t*, const uint8_t*, const uint64_t*, const uint32_t*,
-                            uint32_t n, uint8_t* tri, int32_t* err, uint64_t* bm, uint32_t stride, hipStream_t, bool) {
-    results(n, tri, err, bm, stride);
+hipError_t launch_eval_scan(const Batch& b, const Results& res, bool, hipStream_t) {
+    results(b.n, res.tri, res.err, res.bm, res.stride);
     return hipSuccess;
 }
-hipError_t launch_select(const uint8_t* const*, const uint32_t*, uint32_t, const uint8_t*, const uint64_t*,
-                         const uint32_t*, uint32_t n, uint32_t* out, uint32_t stride, uint64_t* rows,
-                         uint32_t row_stride, uint32_t* slow_count, uint32_t*, const uint32_t*, uint8_t*, uint32_t,
-                         hipStream_t) {
-    if (rows) {
-        *slow_count = 0;
-        for (uint32_t r = 0; r < n; r++) rows[(size_t)r * row_stride] = r;
+hipError_t launch_select(const Batch& b, uint32_t, const Values& v, const Work& work, const uint32_t*, hipStream_t) {
+    if (work.rows) {
+        *work.slow_count = 0;
+        for (uint32_t r = 0; r < b.n; r++) work.rows[(size_t)r * work.row_stride] = r;
     }
-    std::memset(out, 0, (size_t)n * stride * 12);
+    std::memset(v.out, 0, (size_t)b.n * v.stride * 12);
     return hipSuccess;
 }
-hipError_t launch_select_rows(const uint8_t* const*, const uint8_t*, const uint64_t*, const uint32_t*, uint32_t n,
-                              uint32_t* out, uint32_t stride, const uint64_t* rows, uint32_t row_stride, uint32_t,
-                              const uint32_t*, bool, hipStream_t) {
-    for (uint32_t r = 0; r < n; r++) out[(size_t)r * stride * 3] = (uint32_t)rows[(size_t)r * row_stride];
+hipError_t launch_select_rows(const Batch& b, const Values& v, const Work& work, uint32_t, const uint32_t*, bool,
+                              hipStream_t) {
+    for (uint32_t r = 0; r < b.n; r++)
+        v.out[(size_t)r * v.stride * 3] = (uint32_t)work.rows[(size_t)r * work.row_stride];
     return hipSuccess;
 }
-hipError_t launch_eval_fast(const uint8_t* const*, const uint32_t*, uint32_t, const uint8_t*, const uint64_t*,
-                            const uint32_t*, uint32_t n, uint8_t* tri, int32_t* err, uint64_t* bm, uint32_t stride,
-                            uint64_t* rows, uint32_t row_stride, uint32_t* slow_count, uint32_t*, hipStream_t, int,
-                            const uint32_t*, bool, bool, uint32_t, const uint32_t*, uint8_t*, uint32_t) {
-    *slow_count = n / 7;
-    for (uint32_t r = 0; r < n; r++) rows[(size_t)r * row_stride] = r;
-    results(n, tri, err, bm, stride);
+hipError_t launch_eval_fast(const Batch& b, const Results& res, const Work& work, const EvalPlan&, const uint32_t*,
+                            const uint32_t*, uint8_t*, hipStream_t) {
+    *work.slow_count = b.n / 7;
+    for (uint32_t r = 0; r < b.n; r++) work.rows[(size_t)r * work.row_stride] = r;
+    results(b.n, res.tri, res.err, res.bm, res.stride);
     return hipSuccess;
 }
 bool stream_eligible(const uint8_t*, uint32_t) { return true; }
 uint32_t stream_records(const uint8_t*) { return 1; }
-hipError_t launch_eval_stream(const uint8_t* const*, const uint32_t*, uint32_t, uint32_t, const uint8_t*,
-                              const uint64_t*, const uint32_t*, uint32_t n, uint8_t* tri, int32_t* err, uint64_t* bm,
-                              uint32_t stride, uint64_t* rows, uint32_t row_stride, bool keep_rows,
-                              uint32_t* stage_ids, uint32_t* slow_count, uint32_t*, hipStream_t, int, bool,
-                              uint32_t, bool* zero) {
+hipError_t launch_eval_stream(const Batch& b, const Results& res, const Work& work, const EvalPlan& plan, uint32_t,
+                              uint32_t, uint32_t*, bool* zero, hipStream_t) {
     // (as the small-batch instance: the counters left zero, the slow count at [3])
-    slow_count[3] = n / 5;
-    slow_count[0] = slow_count[1] = slow_count[2] = 0;
-    if (zero) *zero = !keep_rows;
-    if (keep_rows) slow_count[0] = n / 5;
-    (void)stage_ids;
-    if (keep_rows)
-        for (uint32_t r = 0; r < n; r++) rows[(size_t)r * row_stride] = r;
-    results(n, tri, err, bm, stride);
+    work.slow_count[3] = b.n / 5;
+    work.slow_count[0] = work.slow_count[1] = work.slow_count[2] = 0;
+    if (zero) *zero = !plan.keep_rows;
+    if (plan.keep_rows) {
+        work.slow_count[0] = b.n / 5;
+        for (uint32_t r = 0; r < b.n; r++) work.rows[(size_t)r * work.row_stride] = r;
+    }
+    results(b.n, res.tri, res.err, res.bm, res.stride);
     return hipSuccess;
 }
-hipError_t launch_len_order(const uint32_t*, uint32_t n, uint32_t* hist, uint32_t* perm, hipStream_t,
-                            uint32_t* pos_of) {
+hipError_t launch_len_order(const uint32_t*, uint32_t n, uint32_t* hist, uint32_t* perm, uint32_t* pos_of,
+                            hipStream_t) {
     hist[0] = n;
     for (uint32_t r = 0; r < n; r++) perm[r] = r;
     if (pos_of)

@@ -521,3 +521,8 @@ extern "C" int ht_eval_stream(void* h, const uint8_t* arena, const uint64_t* off
     }
     return 0;
 }
+
+// the launch plan (ajx_plan.h): which kernel a batch gets, as the library decides it
+#include "../../authorino_amd/csrc/ajx_plan.h"
+extern "C" void ht_plan_eval(const ajx::PlanIn* in, ajx::EvalPlan* out) { *out = ajx::plan_eval(*in); }
+extern "C" int ht_mode_known(int mode) { return ajx::mode_known(mode) ? 1 : 0; }

@@ -193,3 +193,34 @@ def test_stream_slow_path_batch_latency(ctx):
     # (one wave walking 4096 exact scans serially took seconds; the grid-stride launch takes
     # milliseconds. The bound is generous so that load on the shared box can not fail it.)
     assert dt < 0.5, dt
+
+
+def test_kernel_modes_by_name_agree_and_unknown_modes_are_refused(ctx):
+    """c2 at 193 requests (three waves and a partial one) under the modes that pick a full
+    kernel by name — 0 the streaming kernel's small-batch instance, 41 the lean kernel, 52
+    the streaming kernel at 32 requests per wave: each equal to the oracle. A retired mode
+    number is refused and leaves the context evaluating under the mode it had."""
+    from authorino_amd import runtime, workloads
+
+    w = workloads.make("c2", n=193)
+    spec = _flat(w.expr)
+    rs = ctx.compile(*spec)
+    otri, oerr, obm = O.eval_batch([O.Ruleset(*spec)], w.arena, w.offs, w.lens, nthreads=8)
+
+    def check(mode):
+        tri, err, bm = ctx.eval_host_arena([rs], w.arena, w.offs, w.lens)
+        assert np.array_equal(tri, otri), mode
+        assert np.array_equal(err, oerr), mode
+        assert np.array_equal(bm[:, :obm.shape[1]], obm), mode
+
+    try:
+        for mode in (0, 41, 52):
+            ctx.set_kernel_mode(mode)
+            check(mode)
+        ctx.set_kernel_mode(0)
+        for mode in (1, 3, 12):
+            with pytest.raises(runtime.AuthjxError):
+                ctx.set_kernel_mode(mode)
+        check(0)
+    finally:
+        ctx.set_kernel_mode(0)
