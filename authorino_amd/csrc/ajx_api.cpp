@@ -16,6 +16,7 @@
 #include "ajx_blob.h"
 #include "ajx_kernels.h"
 #include "ajx_batcher.h"
+#include "ajx_render_api.h"
 
 struct authjx_ruleset {
     int device = 0;
@@ -121,6 +122,10 @@ struct authjx_ctx {
     uint32_t stream_max_n = 4096;
     int mode = ajx::kModeDefault;  // profiling / comparison only: an ajx::KernelMode (ajx_plan.h)
 };
+
+// for the render entry points (ajx_render_api.cpp, ajx_render_api.h)
+int ajx_ctx_device(const authjx_ctx* ctx) { return ctx->device; }
+hipStream_t ajx_ctx_stream(const authjx_ctx* ctx) { return ctx->stream; }
 
 namespace {
 

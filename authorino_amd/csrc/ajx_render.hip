@@ -1,0 +1,42 @@
+// ajx_render.hip — the render kernel: selected values -> final response header bytes
+// (ajx_render.h). One work-item per request, in request order, 256-thread workgroups; the
+// container walk's level stack lives in LDS (kMaxRenderDepth levels of three words per
+// lane, 24 KiB per workgroup), never in a runtime-indexed register array.
+#include <hip/hip_runtime.h>
+
+#include "ajx_render.h"
+#include "ajx_render_api.h"
+
+namespace ajx {
+
+constexpr uint32_t kRenderBlock = 256;
+
+__global__ __launch_bounds__(256) void ajx_render_values(const uint8_t* __restrict__ prog,
+                                                         const uint8_t* __restrict__ arena,
+                                                         const uint64_t* __restrict__ offs,
+                                                         const uint32_t* __restrict__ lens, uint32_t n,
+                                                         const uint32_t* __restrict__ values, uint32_t values_stride,
+                                                         const uint8_t* __restrict__ text, uint32_t text_stride,
+                                                         uint8_t* __restrict__ out_text, uint32_t out_stride,
+                                                         uint32_t* __restrict__ out, uint32_t n_outputs) {
+    __shared__ uint32_t levels[kMaxRenderDepth * kRenderLevelWords * kRenderBlock];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const RenderStack st{levels + threadIdx.x, kRenderBlock};
+    render_request(prog, arena + offs[r], lens[r], values + (size_t)r * values_stride * 3u,
+                   text ? text + (size_t)r * text_stride : nullptr, text_stride, out_text + (size_t)r * out_stride,
+                   out_stride, out + (size_t)r * n_outputs * 3u, st);
+}
+
+hipError_t launch_render(const uint8_t* d_prog, uint32_t n_outputs, const uint8_t* arena, const uint64_t* offs,
+                         const uint32_t* lens, uint32_t n, const uint32_t* values, uint32_t values_stride,
+                         const uint8_t* text, uint32_t text_stride, uint8_t* out_text, uint32_t out_stride,
+                         uint32_t* out, hipStream_t stream) {
+    if (n == 0 || n_outputs == 0) return hipSuccess;
+    const uint32_t grid = (n + kRenderBlock - 1) / kRenderBlock;
+    hipLaunchKernelGGL(ajx_render_values, dim3(grid), dim3(kRenderBlock), 0, stream, d_prog, arena, offs, lens, n,
+                       values, values_stride, text, text_stride, out_text, out_stride, out, n_outputs);
+    return hipGetLastError();
+}
+
+}  // namespace ajx

@@ -1,0 +1,24 @@
+// ajx_render_api.h — private: what the render entry points (ajx_render_api.cpp, a
+// translation unit of its own) need from the rest of the library.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/authjx.h"
+
+// the context's device and its own stream (ajx_api.cpp)
+int ajx_ctx_device(const authjx_ctx* ctx);
+hipStream_t ajx_ctx_stream(const authjx_ctx* ctx);
+
+namespace ajx {
+
+// The render kernel (ajx_render.hip): request r renders the program's outputs from
+// values[r * values_stride ...] into out_text[r * out_stride ...] and writes n_outputs
+// records {start, len, status} at out[r * n_outputs ...]. text: the requests' text slots or
+// nullptr. out_text 16-byte aligned, out_stride a multiple of 16.
+hipError_t launch_render(const uint8_t* d_prog, uint32_t n_outputs, const uint8_t* arena, const uint64_t* offs,
+                         const uint32_t* lens, uint32_t n, const uint32_t* values, uint32_t values_stride,
+                         const uint8_t* text, uint32_t text_stride, uint8_t* out_text, uint32_t out_stride,
+                         uint32_t* out, hipStream_t stream);
+
+}  // namespace ajx

@@ -48,7 +48,14 @@ import numpy as np
 from . import jsonexp
 from .authorization import JSONPatternMatching, UnauthorizedError
 from .cache import EvaluatorCache, is_hit
-from .response import JSONValue, ResponseConfig, ResponseSelectors, ValueSelectors, stringify_json, wrap_responses
+from .response import (HTTP_HEADER_WRAPPER, JSONValue, ResponseConfig, ResponseSelectors, ValueSelectors,
+                       stringify_json, wrap_responses)
+
+
+class _RenderedHeader(str):
+    """A header value the device rendered (ResponseSelectors.render): final text, not an
+    object WrapObjectAsHeaderValue still has to format."""
+
 
 UNMATCHING_CONDITIONS = "unmatching conditions for config"
 CODE_OK = 0  # rpc.OK
@@ -378,8 +385,16 @@ class AuthPipelineBatch:
         spans = self.selectors.resolve(sub, arena, offs, lens)
         if spans.unresolved().any():
             raise runtime.AuthjxError("device could not resolve a response selector")
+        # header text from the device (authjx_render_batch) where the context offers it: every
+        # httpHeader-wrapped config's value per request; an output the device declines, and
+        # every dynamic-metadata config, goes through call() + wrap_responses below
+        text = out_of = None
+        if hasattr(self.ctx, "render_host_arena") and any(c.wrapper == HTTP_HEADER_WRAPPER
+                                                           for c in self.selectors.configs):
+            _, out_of = self.selectors._render_program()
+            text, _ = self.selectors.render(arena, offs, lens, spans)
+            out_of = {id(c): out_of[ci] for ci, c in enumerate(self.selectors.configs) if ci in out_of}
         granted = [dict() for _ in sub]
-        idx = np.arange(len(sub))
         for level in self.response_levels:
             conds = [c.conditions for c in level if c.conditions is not None]
             met = {}
@@ -389,11 +404,31 @@ class AuthPipelineBatch:
                 met = {id(e): tri[j] == runtime.T for j, e in enumerate(conds)}
             for c in level:
                 ok = met[id(c.conditions)] if c.conditions is not None else None
+                k = out_of.get(id(c)) if out_of is not None else None
                 for j in range(len(sub)):
                     if ok is None or ok[j]:
+                        if k is not None and text[j][k] is not None:
+                            granted[j][c.name] = (c, _RenderedHeader(text[j][k].decode("utf-8", "replace")))
+                            self.selectors.rendered += 1
+                            continue
+                        if k is not None:
+                            self.selectors.fallbacks += 1
                         granted[j][c.name] = (c, self.selectors.call(c, sub[j], spans[j]))
         for j, i in enumerate(live.tolist()):
-            results[i].headers, results[i].metadata = wrap_responses(granted[j])
+            # (a header the device rendered is already WrapObjectAsHeaderValue's text)
+            dev = {n: v for n, v in granted[j].items() if isinstance(v[1], _RenderedHeader)}
+            if not dev:
+                results[i].headers, results[i].metadata = wrap_responses(granted[j])
+                continue
+            headers, metadata = {}, {}
+            for n, (c, obj) in granted[j].items():  # evaluators.WrapResponses' order
+                if n in dev:
+                    headers[c.wrapper_key] = str(obj)
+                else:
+                    h, m = wrap_responses({n: (c, obj)})
+                    headers.update(h)
+                    metadata.update(m)
+            results[i].headers, results[i].metadata = headers, metadata
 
 
 def evaluate_json_authorization(rules: Optional[jsonexp.Expression], docs: Sequence):

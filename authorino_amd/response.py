@@ -15,6 +15,12 @@ into Go values (gjson `Result.Value()` / `Result.String()`) and formats the head
 (`fmt.Sprintf("%v")` or `json.Marshal`), which is per-output string building, not a scan.
 There is no CPU path for the lookup: without the HIP library the calls raise.
 
+The header text itself can come from the device as well: compile_render turns the
+httpHeader-wrapped configs into a render program (authjx_render_*, csrc/ajx_render.h) whose
+ops restate result_string, go_sprint_v and go_json_marshal over the selected values;
+ResponseSelectors.render runs it. The functions here stay the executable specification,
+and the fallback for an output the device declines.
+
 Go formatting restated here (Go 1.21):
   * fmt %v of float64 = strconv.FormatFloat(f, 'g', -1, 64): shortest digits, %e form
     when the decimal exponent is < -4 or >= 6 (1685557675 -> "1.685557675e+09")
@@ -603,6 +609,8 @@ class ResponseSelectors(ValueSelectors):
 
     def __init__(self, configs: Sequence[ResponseConfig], ctx):
         self.configs = list(configs)
+        self._render = None
+        self.rendered = self.fallbacks = 0  # header values taken from the device / left to the host
         super().__init__([v for c in self.configs for v in c.values()], ctx, "response selectors")
 
     def call(self, c: ResponseConfig, doc: bytes, spans_r) -> object:
@@ -612,6 +620,113 @@ class ResponseSelectors(ValueSelectors):
         if c.plain is not None:
             return self._value(c.plain, doc, spans_r)
         return None
+
+
+    # ---- header values rendered on the device (authjx_render_*) ----
+    # bytes of rendered header text per request; a request whose headers do not fit renders
+    # those that do, the rest on the host
+    RENDER_STRIDE = 1024
+
+    def _render_program(self):
+        """The render program of the httpHeader-wrapped configs, compiled on first use:
+        (device program, {config index: output index})."""
+        if self._render is None:
+            ops, _ = compile_render(self.configs, self)
+            index, k = {}, 0
+            for ci, c in enumerate(self.configs):
+                if c.wrapper == HTTP_HEADER_WRAPPER:
+                    index[ci] = k
+                    k += 1
+            self._render = (self.ctx.compile_render(ops.outputs, ops.n_slots), index)
+        return self._render
+
+    def render(self, arena, offs, lens, selected: Selected, out_stride: Optional[int] = None):
+        """The header text of every httpHeader-wrapped config for each request, from the
+        device: (values[r][k] = bytes or None, status u32[n][n_outputs]); None where the
+        device declined (RENDER_UNRENDERED: the caller renders that header from call())."""
+        prog, _ = self._render_program()
+        rec, text = self.ctx.render_host_arena(prog, arena, offs, lens, selected.spans, selected.text,
+                                               out_stride=out_stride or self.RENDER_STRIDE)
+        values = []
+        for r in range(len(rec)):
+            row = text[r]
+            values.append([row[int(s):int(s) + int(ln)].tobytes() if st == RENDER_OK else None
+                           for s, ln, st in rec[r]])
+        return values, rec[:, :, 2]
+
+
+# authjx_render_op.op / authjx_rendered.status (include/authjx.h AUTHJX_R_*, AUTHJX_RENDER_*)
+R_LIT, R_STRING, R_STRING_ESC, R_SPRINT, R_MARSHAL = range(5)
+RENDER_OK, RENDER_UNRENDERED = 0, 1
+
+
+@dataclass
+class RenderOps:
+    """A render program before it is handed to the device: per output (header) a list of
+    (R_LIT, bytes) | (R_STRING | R_STRING_ESC | R_SPRINT | R_MARSHAL, value slot)."""
+
+    outputs: List[List[Tuple[int, object]]]
+    n_slots: int
+
+
+def _add_lit(ops: list, b: bytes) -> None:
+    if not b:
+        return
+    if ops and ops[-1][0] == R_LIT:
+        ops[-1] = (R_LIT, ops[-1][1] + b)
+    else:
+        ops.append((R_LIT, b))
+
+
+def compile_render(configs: Sequence[ResponseConfig], selectors: ValueSelectors) -> Tuple[RenderOps, List[str]]:
+    """The render program of the httpHeader-wrapped configs (one output each, in config
+    order) over `selectors`' value slots, and the outputs' header keys. What depends only
+    on the config is rendered here: template literals, static values (go_sprint_v /
+    go_json_marshal), DynamicJSON property names in key order with the last duplicate kept
+    (the evaluator returns a Go map). The envoyDynamicMetadata wrapper yields objects, not
+    text: those configs have no output."""
+    outputs, keys = [], []
+    for c in configs:
+        if c.wrapper != HTTP_HEADER_WRAPPER:
+            continue
+        ops: list = []
+        if c.json_properties is not None:
+            props = dict(c.json_properties)
+            try:
+                _add_lit(ops, b"{")
+                for i, name in enumerate(sorted(props, key=lambda s: s.encode())):
+                    v = props[name]
+                    _add_lit(ops, (b"," if i else b"") + _json_string(name).encode() + b":")
+                    if not v.pattern:
+                        _add_lit(ops, go_json_marshal(v.static).encode())
+                    elif v.is_template():
+                        _add_lit(ops, b'"')
+                        for kind, s in template_segments(v.pattern):
+                            if kind == "lit":
+                                _add_lit(ops, _json_string(s)[1:-1].encode())
+                            else:
+                                ops.append((R_STRING_ESC, selectors._slot[s]))
+                        _add_lit(ops, b'"')
+                    else:
+                        ops.append((R_MARSHAL, selectors._slot[v.pattern]))
+                _add_lit(ops, b"}")
+            except _UnsupportedValue:  # a static json.Marshal rejects: StringifyJSON gives ""
+                ops = []
+        elif c.plain is not None and c.plain.pattern:
+            v = c.plain
+            if v.is_template():
+                for kind, s in template_segments(v.pattern):
+                    if kind == "lit":
+                        _add_lit(ops, s.encode())
+                    else:
+                        ops.append((R_STRING, selectors._slot[s]))
+            else:
+                ops.append((R_SPRINT, selectors._slot[v.pattern]))
+        else:
+            _add_lit(ops, go_sprint_v(c.plain.static if c.plain is not None else None).encode())
+        outputs.append(ops)
+        keys.append(c.wrapper_key)
+    return RenderOps(outputs, len(selectors.paths)), keys
 
 
 def wrap_responses(responses: Dict[str, Tuple[ResponseConfig, object]]):

@@ -42,6 +42,18 @@ class _Tree(C.Structure):
                 ("nodes", C.POINTER(_Node)), ("n_nodes", C.c_uint32), ("root", C.c_int32)]
 
 
+class _RenderOp(C.Structure):
+    _fields_ = [("op", C.c_uint8), ("slot", C.c_uint32), ("lit", C.c_char_p), ("lit_len", C.c_uint32)]
+
+
+class _RenderOutput(C.Structure):
+    _fields_ = [("ops", C.POINTER(_RenderOp)), ("n_ops", C.c_uint32)]
+
+
+# authjx_render_op.op (AUTHJX_R_*) and authjx_rendered.status (AUTHJX_RENDER_*)
+R_LIT, R_STRING, R_STRING_ESC, R_SPRINT, R_MARSHAL = range(5)
+RENDER_OK, RENDER_UNRENDERED = 0, 1
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -56,6 +68,8 @@ EXPORTS = [
     "authjx_batcher_stats",
     "authjx_index_new", "authjx_index_free", "authjx_index_set", "authjx_index_delete_key", "authjx_index_get",
     "authjx_index_lookup_batch", "authjx_pack_json", "authjx_build_hash",
+    "authjx_render_compile", "authjx_render_free", "authjx_render_outputs", "authjx_render_batch_device",
+    "authjx_render_batch",
 ]
 
 
@@ -175,6 +189,23 @@ def load_library(path: str = LIB_PATH):
         L.authjx_pack_json.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                        C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32]
         L.authjx_pack_json.restype = C.c_int
+        # (an AUTHJX_LIB build of an earlier tree may lack the render entry points)
+        if os.environ.get("AUTHJX_LIB") is None or hasattr(L, "authjx_render_compile"):
+            L.authjx_render_compile.argtypes = [C.c_void_p, C.POINTER(_RenderOutput), C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
+            L.authjx_render_compile.restype = C.c_int
+            L.authjx_render_free.argtypes = [C.c_void_p]
+            L.authjx_render_free.restype = None
+            L.authjx_render_outputs.argtypes = [C.c_void_p]
+            L.authjx_render_outputs.restype = C.c_uint32
+            L.authjx_render_batch_device.argtypes = [
+                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.authjx_render_batch_device.restype = C.c_int
+            L.authjx_render_batch.argtypes = [
+                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.authjx_render_batch.restype = C.c_int
         L.authjx_debug_last_error.argtypes = []
         L.authjx_debug_last_error.restype = C.c_char_p
         _lib = L
@@ -388,6 +419,53 @@ class Context:
         _check(rc, "authjx_select_batch")
         return out[:n]
 
+    def compile_render(self, outputs, n_slots: int) -> "RenderProgram":
+        """authjx_render_compile: outputs = [[(R_LIT, bytes) | (R_STRING.., slot), ...], ...]."""
+        return RenderProgram(self, outputs, n_slots)
+
+    def render_device(self, prog: "RenderProgram", arena, offs, lens, values, out_text, out, text=None,
+                      stream=None) -> None:
+        """authjx_render_batch_device on HBM-resident torch tensors: values u32[n][stride][3]
+        (a select call's output), text u8[n][text_stride] or None, out_text u8[n][out_stride]
+        (out_stride a multiple of 16), out u32[n][n_outputs][3] = {start, len, status}.
+        Asynchronous; order it after the select on the same stream."""
+        n = int(lens.numel())
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        rc = load_library().authjx_render_batch_device(
+            self._h, prog._h, ptr(arena), ptr(offs), ptr(lens), n, ptr(values), int(values.shape[1]), ptr(text),
+            int(text.shape[1]) if text is not None else 0, ptr(out_text), int(out_text.shape[1]), ptr(out),
+            C.c_void_p(stream) if stream else None)
+        _check(rc, "authjx_render_batch_device")
+
+    def render_host_arena(self, prog: "RenderProgram", arena, offs, lens, values, text=None, out_stride: int = 4096,
+                          out_text=None):
+        """authjx_render_batch: (u32[n][n_outputs][3] records {start, len, status}, u8[n][out_stride]
+        output slots). out_text: the slots to render into (their bytes outside the outputs are
+        kept), else fresh ones."""
+        n = int(lens.shape[0])
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        if arena.nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        stride = int(values.shape[1]) if values.ndim == 3 else 0
+        if text is not None:
+            text = np.ascontiguousarray(text, dtype=np.uint8)
+        if out_text is None:
+            out_text = np.zeros((max(n, 1), out_stride), dtype=np.uint8)
+        assert out_text.dtype == np.uint8 and out_text.flags.c_contiguous and out_text.shape[0] >= n
+        rec = np.zeros((max(n, 1), max(prog.n_outputs, 1), 3), dtype=np.uint32)
+        rc = load_library().authjx_render_batch(
+            self._h, prog._h, C.c_void_p(arena.ctypes.data), int(arena.nbytes), C.c_void_p(offs.ctypes.data),
+            C.c_void_p(lens.ctypes.data), n, C.c_void_p(values.ctypes.data), stride,
+            C.c_void_p(text.ctypes.data) if text is not None else None,
+            int(text.shape[1]) if text is not None else 0, C.c_void_p(out_text.ctypes.data),
+            int(out_text.shape[1]), C.c_void_p(rec.ctypes.data))
+        _check(rc, "authjx_render_batch")
+        rec[:, :, 2] &= 0xFF  # (status is a byte; the three after it are reserved)
+        return rec[:n, :prog.n_outputs], out_text
+
     def release_stream(self, stream) -> None:
         """authjx_release_stream: free the workspace kept for a (short-lived) stream."""
         L = load_library()
@@ -457,6 +535,44 @@ class Ruleset:
         if getattr(self, "_h", None):
             try:
                 load_library().authjx_free(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
+class RenderProgram:
+    """A render program resident in HBM (authjx_render_compile / authjx_render_free): one
+    output per response header, each a list of (R_LIT, bytes) | (op, value slot)."""
+
+    def __init__(self, ctx: Context, outputs, n_slots: int):
+        L = load_library()
+        self.ctx = ctx
+        keep = []
+        oarr = (_RenderOutput * max(len(outputs), 1))()
+        for k, ops in enumerate(outputs):
+            arr = (_RenderOp * max(len(ops), 1))()
+            for q, (op, arg) in enumerate(ops):
+                if int(op) == R_LIT:
+                    lit = bytes(arg)
+                    keep.append(lit)
+                    arr[q] = _RenderOp(R_LIT, 0, lit, len(lit))
+                else:
+                    arr[q] = _RenderOp(int(op), int(arg), None, 0)
+            keep.append(arr)
+            oarr[k] = _RenderOutput(arr, len(ops))
+        err = C.create_string_buffer(256)
+        h = C.c_void_p()
+        rc = L.authjx_render_compile(ctx._h, oarr, len(outputs), int(n_slots), C.byref(h), err, 256)
+        if rc != 0:
+            raise AuthjxError(f"authjx_render_compile failed ({rc}): {err.value.decode(errors='replace')}")
+        self._h = h
+        self.n_outputs = int(L.authjx_render_outputs(h))
+        self.n_slots = int(n_slots)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                load_library().authjx_render_free(self._h)
             except Exception:
                 pass
             self._h = None

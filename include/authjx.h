@@ -359,6 +359,78 @@ int authjx_pack_json(const uint8_t* tapes, const uint64_t* tape_offs, const uint
                      uint8_t* arena, uint64_t arena_cap, uint64_t* out_offs, uint32_t* out_lens,
                      uint64_t* out_total, uint32_t n_threads);
 
+/* Response header values rendered on the device. The select entry points return spans; a
+ * render program, compiled once per AuthConfig, turns them into the bytes Authorino puts on
+ * the wire: a Plain header (fmt.Sprintf("%v", gjson Value())), a template
+ * (ReplaceJSONPlaceholders, pkg/json/json.go:96-151) or a DynamicJSON header (json.Marshal
+ * of a map, then StringifyJSON). A program is a list of outputs (one per header), each a
+ * list of ops over value slots: indices into the authjx_value[n][values_stride] array a
+ * select call wrote (source bytes: the document, or the request's text slot when esc has
+ * AUTHJX_VALUE_TEXT). Ops append:
+ *   AUTHJX_R_LIT         lit[0, lit_len): template text, pre-rendered statics, {"name": scaffolding
+ *   AUTHJX_R_STRING      gjson Result.String() of the value (a template placeholder)
+ *   AUTHJX_R_STRING_ESC  the same bytes with encoding/json's string escaping, no quotes (a
+ *                        template that is a DynamicJSON property value)
+ *   AUTHJX_R_SPRINT      fmt.Sprintf("%v", Result.Value()): numbers through float64 and %g
+ *                        (1685557675 -> 1.685557675e+09), nil "<nil>", arrays "[a b]", objects
+ *                        "map[k:v k:v]" with keys sorted by bytes, the last duplicate kept
+ *   AUTHJX_R_MARSHAL     json.Marshal(Result.Value()): HTML-safe string escapes, float64
+ *                        numbers ('e' form below 1e-6 and from 1e21), sorted object keys. A
+ *                        NaN / Inf under it makes Marshal fail: the whole output is empty,
+ *                        status AUTHJX_RENDER_OK (StringifyJSON's error is dropped)
+ * Each output of each request has a status. AUTHJX_RENDER_UNRENDERED: the caller renders
+ * that header itself; the output appended nothing and the request's other outputs are not
+ * disturbed. The reasons: a slot value of type AUTHJX_JSON_UNSUPPORTED; a number the device
+ * leaves undecided (a hex mantissa or a '_' separator); containers nested deeper than 8
+ * levels under SPRINT / MARSHAL; bytes that are not UTF-8 under STRING_ESC or MARSHAL's
+ * string encoding; the output does not fit what is left of the request's output slot. */
+#define AUTHJX_R_LIT 0
+#define AUTHJX_R_STRING 1
+#define AUTHJX_R_STRING_ESC 2
+#define AUTHJX_R_SPRINT 3
+#define AUTHJX_R_MARSHAL 4
+#define AUTHJX_RENDER_OK 0
+#define AUTHJX_RENDER_UNRENDERED 1
+typedef struct authjx_render authjx_render;
+typedef struct {
+    uint8_t op;         /* AUTHJX_R_* */
+    uint32_t slot;      /* value slot (every op but LIT) */
+    const uint8_t* lit; /* LIT: the bytes (copied by the compile) */
+    uint32_t lit_len;
+} authjx_render_op;
+typedef struct {
+    const authjx_render_op* ops;
+    uint32_t n_ops;
+} authjx_render_output;
+typedef struct {
+    uint32_t start, len; /* within the request's output slot */
+    uint8_t status;      /* AUTHJX_RENDER_* */
+    uint8_t reserved[3];
+} authjx_rendered;
+/* AUTHJX_EINVAL (and a message in errbuf) for an unknown op or a slot >= n_slots. */
+int authjx_render_compile(authjx_ctx* ctx, const authjx_render_output* outs, uint32_t n_outputs, uint32_t n_slots,
+                          authjx_render** out, char* errbuf, size_t errcap);
+void authjx_render_free(authjx_render* prog);
+uint32_t authjx_render_outputs(const authjx_render* prog);
+/* Device buffers, asynchronous on `stream` (NULL: the context's stream); order it after
+ * the select call that wrote d_values. d_text may be NULL when no value has
+ * AUTHJX_VALUE_TEXT. d_out[r * n_outputs + k] is output k of request r, its bytes at
+ * d_out_text[r * out_stride + start ...]; a request's outputs follow each other in its
+ * slot, and the slot's bytes past the last output are unspecified. Nothing outside
+ * [r * out_stride, (r + 1) * out_stride) is read or written. AUTHJX_EINVAL when
+ * values_stride is below the program's n_slots, out_stride is 0 or no multiple of 16, or
+ * d_out_text is not 16-byte aligned. */
+int authjx_render_batch_device(authjx_ctx* ctx, const authjx_render* prog, const uint8_t* d_arena,
+                               const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
+                               const authjx_value* d_values, uint32_t values_stride, const uint8_t* d_text,
+                               uint32_t text_stride, uint8_t* d_out_text, uint32_t out_stride,
+                               authjx_rendered* d_out, void* stream);
+/* Same from host buffers (out_text needs no alignment); synchronous. */
+int authjx_render_batch(authjx_ctx* ctx, const authjx_render* prog, const uint8_t* arena, uint64_t arena_len,
+                        const uint64_t* offs, const uint32_t* lens, uint32_t n, const authjx_value* values,
+                        uint32_t values_stride, const uint8_t* text, uint32_t text_stride, uint8_t* out_text,
+                        uint32_t out_stride, authjx_rendered* out);
+
 #ifdef __cplusplus
 }
 #endif
