@@ -45,12 +45,45 @@ namespace lean {
 inline uint64_t g_lean_iters = 0, g_lean_subs = 0;  // (host test builds: walker iterations, sub-windows)
 inline uint32_t* g_lean_trace = nullptr;  // (host test builds: sub-window << 8 | token kind per iteration)
 inline uint32_t g_lean_trace_n = 0, g_lean_trace_cap = 0;
+// (a second word per traced iteration, when set: the token's doc position (24 bits) |
+// kTraceElig when the walk of the sub-window before its own could have taken it (the
+// eligibility rules at Walk::walk's loop) | kTraceStop when the lane takes no token early
+// after it (squashing, or the walk ended) | kTraceEarly when it was taken early |
+// kTraceSplit for a key whose string value closes in the sub-window after its own (taken
+// early, the value would go pending and its closing quote be a token of its own))
+inline uint32_t* g_lean_trace_pos = nullptr;
+constexpr uint32_t kTraceElig = 1u << 24, kTraceStop = 1u << 25, kTraceEarly = 1u << 26;
+constexpr uint32_t kTraceSplit = 1u << 27;
+// The spare budget of the host builds. On the device a lane whose own tokens are gone runs
+// on while some lane of its wave has tokens left, and takes tokens of the next sub-window
+// in those iterations; a host lane has no wave, so a test gives it spare iterations per
+// walk() call instead: policy 0 none (the default: the walk of one lane alone), 1 a fixed
+// g_lean_spare_k, 2 unlimited, 3 drawn per call from g_lean_spare_rng (0..4, xorshift).
+#if !defined(AJX_LEAN_SPARE_DEFAULT)
+#define AJX_LEAN_SPARE_DEFAULT 0
+#endif
+inline uint32_t g_lean_spare_policy = AJX_LEAN_SPARE_DEFAULT, g_lean_spare_k = 0;
+inline uint64_t g_lean_spare_rng = 1, g_lean_early = 0;  // (g_lean_early: tokens taken early)
+inline uint32_t lean_spare_draw() {
+    if (g_lean_spare_policy == 1) return g_lean_spare_k;
+    if (g_lean_spare_policy == 2) return ~0u;
+    if (g_lean_spare_policy != 3) return 0;
+    uint64_t x = g_lean_spare_rng;
+    x ^= x << 13, x ^= x >> 7, x ^= x << 17;
+    g_lean_spare_rng = x;
+    return (uint32_t)((x >> 33) % 5u);
+}
 #define AJX_LEAN_TICK(x) (x)++
-#define AJX_LEAN_TRACE(k) \
-    (g_lean_trace && g_lean_trace_n < g_lean_trace_cap ? (void)(g_lean_trace[g_lean_trace_n++] = (uint32_t)(g_lean_subs << 8 | (k))) : (void)0)
+#define AJX_LEAN_TRACE(k, pos) \
+    (g_lean_trace && g_lean_trace_n < g_lean_trace_cap \
+         ? (void)((g_lean_trace_pos ? (void)(g_lean_trace_pos[g_lean_trace_n] = (pos)) : (void)0), \
+                  g_lean_trace[g_lean_trace_n++] = (uint32_t)(g_lean_subs << 8 | (k))) \
+         : (void)0)
+#define AJX_LEAN_SPARE() lean_spare_draw()
 #else
 #define AJX_LEAN_TICK(x) ((void)0)
-#define AJX_LEAN_TRACE(k) ((void)0)
+#define AJX_LEAN_TRACE(k, pos) ((void)0)
+#define AJX_LEAN_SPARE() 0u
 #endif
 // (token kinds of the trace: 0 squashed, 1 string element, 2 a key's string value from an
 // earlier sub-window, 3 key + string, 4 key + container, 5 key + scalar, 6 root, 7 element
@@ -354,6 +387,17 @@ struct Walk {
         }
     }
 
+    // May the walk of the sub-window before l take l's token at bit j early? Only when all
+    // that its iteration reads and decides lies inside l (the rules at walk's loop).
+    AJX_HD static bool early_ok(const Sub& l, uint32_t j) {
+        if (j >= 31) return false;  // (the colon-after bit of l's last byte is the next sub-window's)
+        const uint32_t v = j + 2u;  // a key's value
+        if ((l.cq >> j) & (l.co >> (j + 1u)) & 1u)
+            return v < 32 && ((((l.oq | l.op) >> v) & 1u) || (l.st & above(v)) != 0);
+        if (!(((l.cq | l.op | l.cl) >> j) & 1u)) return (l.st & above(j)) != 0;  // a scalar element
+        return true;
+    }
+
     // Walk sub-window c (l: the one after it; its tokens may be taken here: l.tok updated).
     // One iteration takes one token of every lane, whatever its kind, through ONE copy of
     // each step: the token's kind decoded into flags, one group of ring reads (the key's last
@@ -396,9 +440,12 @@ struct Walk {
         } else {
             T = c.tok;
         }
-        const uint32_t cok = (c.co >> 1) | (l.co << 31);  // bit i: a colon at byte i + 1
         const uint32_t cb = (uint32_t)c.base;
-        const uint64_t cl64 = (uint64_t)c.cl | ((uint64_t)l.cl << 32);
+        // c's and l's masks as one: bit i is doc byte cb + i (the register pairs as they are:
+        // a shifted copy of one, the colon-after mask, cost the c2 instance two spilled VGPRs)
+        const uint64_t cq64 = (uint64_t)c.cq | ((uint64_t)l.cq << 32), op64 = (uint64_t)c.op | ((uint64_t)l.op << 32);
+        const uint64_t cl64 = (uint64_t)c.cl | ((uint64_t)l.cl << 32), oq64 = (uint64_t)c.oq | ((uint64_t)l.oq << 32);
+        const uint64_t co64 = (uint64_t)c.co | ((uint64_t)l.co << 32);
         constexpr uint32_t kNone = 0xFFFFFFFFu;
         // escapes are rare: has_bs is skipped, as a branch of the whole wave, unless some lane
         // has a backslash in c or l, or one before c inside the string that is open at c's
@@ -409,15 +456,59 @@ struct Walk {
         const bool bsw = any_lane((c.bs | l.bs) != 0 || lbs1 > carry_oq);
 #endif
         AJX_LEAN_TICK(g_lean_subs);
-        while (T) {
+        // The token loop runs while some lane of the wave has a token of c left (one ballot,
+        // a uniform branch). A lane whose own are gone takes l's tokens in those iterations,
+        // in document order as ever, instead of idling: T64's high half is
+        // l.tok. It takes l's next token early only when early_ok holds for it, never skips
+        // one, and stops for the rest of this walk at the first that has to wait (go), when
+        // it squashes a container (the next walk's preamble goes on from skips) and when its
+        // walk ends. What the iteration of an early token reads lies at or before l's last
+        // byte (cb + 63); ring bytes past that may be stale or in flight, and, as for c's
+        // tokens whose values end near l's end, only reads that a length bounds reach them:
+        //   * the colon-after bit is that of byte p + 1: the token at l's last byte waits;
+        //   * a key's value starts at p + 2: a key at l's last three bytes waits (its string
+        //     value that does not close in l goes pending, as one of c's that does not close
+        //     in c | l; its container value is opened, and squashed from the next walk on);
+        //   * a scalar (a key's value, an array element) needs its end, a structural byte of
+        //     l after it: without one it waits (for a token of c that is a failure of the
+        //     lean scan: longer than two sub-windows);
+        //   * the closing brackets after the value are taken up to l's end, as for c's;
+        //   * carry_oq and lbs1 stay those of c's start: the 64-bit oq and bs masks cover a
+        //     key or string that starts in c and ends at a token of l.
+        // The host builds (one lane) get their spare iterations from AJX_LEAN_SPARE.
+        uint64_t T64 = (uint64_t)T | ((uint64_t)l.tok << 32);
+#if defined(AJX_LEAN_AB_NO_BORROW)  // (A/B builds: DESIGN §5.11; the 64-bit loop alone)
+        bool go = false;
+#else
+        bool go = !skipw;
+#endif
+        uint32_t spare = AJX_LEAN_SPARE();
+        (void)spare;
+        for (;;) {
+            const bool own = (uint32_t)T64 != 0;
+#if defined(AJX_LEAN_AB_NO_BORROW)
+            if (!own) break;
+#elif defined(__HIP_DEVICE_COMPILE__)
+            if (!any_lane(own)) break;
+#else
+            if (!own && !(go && T64 && spare)) break;
+            if (!own) spare--;
+#endif
+            const uint32_t i = (uint32_t)__builtin_ctzll(T64 | (1ull << 63));
+            if (!own) go = go && T64 && early_ok(l, i - 32u);
+            if (!own && !go) continue;  // (this lane idles: the wave's busiest goes on)
             AJX_LEAN_TICK(g_lean_iters);
-            const uint32_t i = ctz(T);
-            T &= T - 1u;
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(AJX_LEAN_COUNT)
+            g_lean_early += own ? 0u : 1u;
+            const uint32_t tr_el = (i >= 32 ? early_ok(l, i - 32u) : early_ok(c, i)) ? kTraceElig : 0u;
+            uint32_t tr_kind = 0, tr_split = 0;
+#endif
+            T64 &= T64 - 1ull;
             const uint32_t p = cb + i;
             uint32_t after = kNone;  // the position after the value this iteration took
             bool bad = false;
             {
-                const bool bq = (c.cq >> i) & 1u, bo = (c.op >> i) & 1u, bc = (c.cl >> i) & 1u, kq = (cok >> i) & 1u;
+                const bool bq = (cq64 >> i) & 1u, bo = (op64 >> i) & 1u, bc = (cl64 >> i) & 1u, kq = ((co64 >> i) >> 1) & 1u;  // (a colon at byte i + 1)
                 const bool root = depth == 0;
                 const bool key = bq && !ta() && expk;  // a key (its closing quote)
                 const bool pv = bq && !ta() && !expk;  // the closing quote of a key's string value
@@ -426,8 +517,8 @@ struct Walk {
                 // a value belongs, the root alone at depth 0
                 bad = root ? !(bo && p == 0) : bq ? kq != key : bc ? false : !ta();
                 // the string's opening quote (a key's, a string element's)
-                const uint32_t oqb = c.oq & below(i);
-                const uint32_t ss = oqb ? cb + hib(oqb) : carry_oq;
+                const uint64_t oqb = oq64 & ((1ull << i) - 1ull);
+                const uint32_t ss = oqb ? cb + 63u - (uint32_t)__builtin_clzll(oqb) : carry_oq;
                 const uint32_t k0 = ss + 1u, klen = p - k0;
                 // the value's start vs (a string's opening quote)
                 const uint32_t vs = key ? p + 2u : pv ? (pend & 0xFFFFFFu) : bq ? ss : p;
@@ -471,14 +562,25 @@ struct Walk {
                 // a key's string value: its closing quote from the masks (or pending)
                 uint32_t e = p;
                 bool ended = true;
-                const uint32_t rv = vs - cb;  // (a key's value: 2..33)
+                const uint32_t rv = vs - cb;  // (a key's value: 2..63; past that only with `bad` set)
                 if (key && vstr) {
-                    const uint64_t m = ((uint64_t)c.cq | ((uint64_t)l.cq << 32)) & (~0ull << (rv + 1));
-                    if (m) {
-                        const uint32_t j = (uint32_t)__builtin_ctzll(m);
-                        if (j < 32) T &= ~(1u << j);
-                        else l.tok &= ~(1u << (j - 32));
+                    // (not at l's last byte: the bit of the colon after that one is the next
+                    // sub-window's, so such a value goes pending and its own token tests it)
+                    // (as `j < 63`: masking bit 63 out of m instead cost the c2 instance two
+                    // spilled VGPRs, with scratch reloads in the window loop)
+                    const uint64_t m = cq64 & ((~0ull << (rv & 63u)) << 1);
+                    const uint32_t j = (uint32_t)__builtin_ctzll(m | (1ull << 63));
+                    if (j < 63) {
+                        T64 &= ~(1ull << j);
                         e = cb + j;
+                        // (a value's closing quote before a colon: the masks allow a colon
+                        // after any closing quote, and a pending value's own token fails it
+                        // below. Taken with its key it must fail too, or a document would go
+                        // to the exact scan or not by where its sub-windows fall)
+                        bad |= ((co64 >> j) >> 1) & 1u;
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(AJX_LEAN_COUNT)
+                        if (i < 32 && j >= 32) tr_split = kTraceSplit;
+#endif
                     } else {
                         ended = false;
                         expk = 0;
@@ -517,17 +619,14 @@ struct Walk {
                     record(s, vs, end, type, vstr && bsw && has_bs(vs, e, c, l) ? 1u : 0u, v0);
                 // a container value
                 if (!bad && vopen) {
-                    if (key) {
-                        if (rv < 32) T &= ~(1u << rv);
-                        else l.tok &= ~(1u << (rv - 32));
-                    }
                     open_f(node, nf, vb == '[', vs);
                     const uint32_t ip = key ? rv : i;
-                    T = ip < 32 ? T & above(ip) : 0u;
+                    T64 = ip < 63 ? T64 & (~0ull << (ip + 1u)) : 0ull;
                     after = vs + 1u;  // (an empty container closes right away)
                     if (skipw) {  // squashed: to its matching bracket, if that lies in c
                         bad |= root;  // (a ruleset whose root node is a leaf)
                         after = kNone;
+                        go = false;
                         if (ip < 32) {
                             uint32_t br = (c.op | c.cl) & above(ip), dep = 1;
                             while (br) {
@@ -537,23 +636,26 @@ struct Walk {
                                 if (dep == 0) {
                                     if (skipw >> 24) record((int32_t)(skipw >> 24) - 1, skips, cb + b + 1u, T_JSON, 0);
                                     skipw = 0;
-                                    T &= above(b);
+                                    T64 &= ~0ull << (b + 1u);  // (b < 32)
                                     after = cb + b + 1u;
+#if !defined(AJX_LEAN_AB_NO_BORROW)
+                                    go = true;
+#endif
                                     break;
                                 }
                             }
-                            if (skipw) {  // (the rest of c lies inside it)
-                                skipw = (skipw & 0xFF000000u) | dep;
-                                T = 0;
-                            }
+                            if (skipw) skipw = (skipw & 0xFF000000u) | dep;  // (the rest of c lies inside it)
                         }
+                        if (skipw) T64 &= ~0xFFFFFFFFull;  // (l's tokens: the next walk's preamble)
                     }
                 }
                 if (!bad && bc) {
                     close(p);
                     after = p + 1u;
                 }
-                AJX_LEAN_TRACE(bc ? 8 : bo ? (root ? 6 : 7) : pv ? 2 : key ? (vstr ? 3 : vopen ? 4 : 5) : bq ? 1 : 9);
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(AJX_LEAN_COUNT)
+                tr_kind = bc ? 8 : bo ? (root ? 6 : 7) : pv ? 2 : key ? (vstr ? 3 : vopen ? 4 : 5) : bq ? 1 : 9;
+#endif
             }
             // the closing brackets that follow the value
             while (!bad && st == S_RUN && after != kNone) {
@@ -561,14 +663,18 @@ struct Walk {
                 if (r >= 64 || !((cl64 >> r) & 1u)) break;
                 bad = depth == 0 || ta() != (rb(after) == ']' ? 1u : 0u) || (!ta() && !expk);
                 if (bad) break;
-                if (r < 32) T &= ~(1u << r);
-                else l.tok &= ~(1u << (r - 32));
+                T64 &= ~(1ull << r);
                 close(after);
                 after++;
             }
             if (bad) st = S_SLOW;
-            if (st != S_RUN) T = 0;
+            if (st != S_RUN) {
+                T64 &= ~0xFFFFFFFFull;
+                go = false;
+            }
+            AJX_LEAN_TRACE(tr_kind, p | tr_el | tr_split | (go ? 0u : kTraceStop) | (own ? 0u : kTraceEarly));
         }
+        l.tok = (uint32_t)(T64 >> 32);
         if (c.oq) carry_oq = (uint32_t)c.base + hib(c.oq);
         if (c.bs) lbs1 = (uint32_t)c.base + hib(c.bs) + 1u;
     }

@@ -9,6 +9,10 @@ the union of the branches its lanes take. The model compares that with other sch
   typed      each step runs ONE kind (the most common among the lanes' next tokens); lanes
              whose next token is another kind wait
   window64   lockstep over 64-byte windows (two sub-windows per loop)
+  borrow     lockstep, and a lane done with its sub-window takes the next one's tokens while
+             the wave's busiest lane goes on, by the walk's own eligibility
+             (the trace's second word: tests/native/lean_borrow.mk's library); `borrow_all`
+             with every token eligible, `decoupled` the busiest lane's tokens per wave
 
   python scripts/sim_walk_sched.py [--workload c2] [--n 8192]
 """
@@ -33,22 +37,87 @@ KIND_ITERS = collections.Counter()  # iterations in which some lane runs each ki
 NKINDS = []
 
 
-def traces(expr, docs):
+ELIG, STOP, SPLIT = 1 << 24, 1 << 25, 1 << 27  # (ajx_lean.h, kTrace*)
+
+
+def traces(exprs, docs):
+    """[(sub-window, kind, flags)] per document; exprs: one expression, or one per document."""
+    import subprocess
+
+    native = os.path.join(ROOT, "tests", "native")
+    subprocess.run(["make", "-s", "-C", native, "-f", "lean_borrow.mk", "libajx_leanborrow.so"], check=True)
+    os.environ["AJX_HOSTTEST_LIB"] = os.path.join(native, "libajx_leanborrow.so")
     import _hosttest as H
 
     L = H.lib()
     L.ht_lean_trace.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
     L.ht_lean_trace.restype = C.c_uint32
-    hr = H.HostRuleset.from_expression(expr)
+    L.ht_lean_trace_pos.argtypes = [C.POINTER(C.c_uint32)]
+    L.ht_lean_trace_pos.restype = None
+    one = not isinstance(exprs, list)
+    hrs = {}
     buf = (C.c_uint32 * (1 << 16))()
+    pos = (C.c_uint32 * (1 << 16))()
+    L.ht_lean_trace_pos(pos)
     out = []
-    for d in docs:
+    for k, d in enumerate(docs):
+        e = exprs if one else exprs[k]
+        if id(e) not in hrs:
+            hrs[id(e)] = H.HostRuleset.from_expression(e)
         L.ht_lean_trace(buf, 1 << 16)
-        H.eval_lean(hr, d, mis=0)
+        H.eval_lean(hrs[id(e)], d, mis=0)
         n = L.ht_lean_trace(None, 0)
         t = np.frombuffer(buf, dtype=np.uint32, count=n).copy()
-        out.append((t >> 8, t & 0xFF))
+        out.append((t >> 8, t & 0xFF, np.frombuffer(pos, dtype=np.uint32, count=n).copy()))
+    L.ht_lean_trace_pos(None)
     return out
+
+
+def borrow_iters(wave, real=True):
+    """Iterations of a wave when a lane whose own tokens of sub-window s are gone takes its
+    tokens of s + 1: one at a time and in order, only eligible ones (real), none after a
+    token that stops it (a squash going on, the walk's end), none while it squashes through
+    s. A key taken early whose string value closes one sub-window on leaves that closing
+    quote as a token of its own (SPLIT)."""
+    lanes = []
+    for sub, kind, fl in wave:
+        lanes.append([[int(s), int(f)] for s, f in zip(sub.tolist(), fl.tolist())])
+    heads = [0] * len(lanes)
+    last_stop = [False] * len(lanes)
+    nsub = max((q[-1][0] for q in lanes if q), default=0) + 2
+    iters = 0
+    for s in range(1, nsub):
+        # (the kernel's go is !skipw after the walk's preamble; the trace knows only that the
+        # lane's last token left it squashing. A squash that ends in s with no own token of
+        # the lane after it leaves the lane free in the kernel and stopped here: the model
+        # errs a little to the pessimistic side)
+        go = []
+        for i, q in enumerate(lanes):
+            h = heads[i]
+            own = h < len(q) and q[h][0] <= s
+            go.append(own or not last_stop[i])
+        while True:
+            if not any(heads[i] < len(q) and q[heads[i]][0] <= s for i, q in enumerate(lanes)):
+                break
+            iters += 1
+            for i, q in enumerate(lanes):
+                h = heads[i]
+                if h >= len(q):
+                    continue
+                ts, f = q[h]
+                if ts <= s:
+                    heads[i] += 1
+                    last_stop[i] = bool(f & STOP)
+                    go[i] = not last_stop[i]
+                elif go[i] and ts == s + 1 and (not real or f & ELIG):
+                    heads[i] += 1
+                    last_stop[i] = bool(f & STOP)
+                    go[i] = not last_stop[i]
+                    if f & SPLIT:  # (the closing quote: a token of s + 2, never at its last byte)
+                        q.insert(heads[i], [s + 2, ELIG])
+                else:
+                    go[i] = False
+    return iters
 
 
 def per_sub(tr, window=1):
@@ -98,19 +167,24 @@ def main():
     w = workloads.make(a.workload, n=a.n, unique=a.n, uniquify=True)
     docs = [w.doc(i) for i in range(w.n)]
     order = np.argsort(-(w.lens.astype(np.int64) >> 3), kind="stable")  # the kernel's length classes
-    trs = traces(w.expr, [docs[i] for i in order])
+    if w.set_of_req is not None:  # (c4: each document with its tenant's ruleset, in the batch's order)
+        order = np.arange(w.n)
+        trs = traces([w.sets[int(w.set_of_req[i])] for i in order], docs)
+    else:
+        trs = traces(w.expr, [docs[i] for i in order])
     kinds = collections.Counter()
-    for _, k in trs:
+    for _, k, _ in trs:
         kinds.update(k.tolist())
     print("tokens per doc:", round(sum(kinds.values()) / len(trs), 1),
           {KINDS[k]: round(v / len(trs), 1) for k, v in sorted(kinds.items())})
     tot = collections.Counter()
     for b in range(0, len(trs) - 63, 64):
         wave = trs[b:b + 64]
-        l1, t1, i1, s1 = wave_costs(wave, 1)
-        l2, _, i2, _ = wave_costs(wave, 2)
+        l1, t1, i1, s1 = wave_costs([t[:2] for t in wave], 1)
+        l2, _, i2, _ = wave_costs([t[:2] for t in wave], 2)
         tot.update({"lock": l1, "typed": t1, "iters": i1, "typed_steps": s1, "win64": l2, "win64_iters": i2,
-                    "waves": 1})
+                    "borrow_iters": borrow_iters(wave), "borrow_all_iters": borrow_iters(wave, real=False),
+                    "decoupled_iters": max(len(t[0]) for t in wave), "waves": 1})
     nw = tot["waves"]
     print({k: round(v / nw, 1) for k, v in tot.items()})
     print("kinds per lockstep iteration:", round(float(np.mean(NKINDS)), 2),
