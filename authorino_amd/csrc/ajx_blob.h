@@ -232,7 +232,8 @@ constexpr uint32_t kLeanArr = 1, kLeanCaps = 2;
 constexpr uint32_t kFlagBufs = 8;  // a selector builds a text (a '#' list): the exact scan's buffers
 // the fold code is one flat All / Any of patterns 0..n_patterns - 1 in order (n_patterns
 // <= 64, one tree): its result is the first pattern, in index order, that is not the
-// group's identity (fold_outputs reads it off the bitmaps, no code interpreted)
+// group's identity (ajx_stageb.h's fold_outputs reads it off the bitmaps, no code
+// interpreted)
 constexpr uint32_t kFlagFlatFold = 16;
 // the fold code is one All / Any whose children are patterns and groups of the other kind
 // over patterns only, patterns 0..n_patterns - 1 in code order (n_patterns <= 64, one

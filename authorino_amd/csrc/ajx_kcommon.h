@@ -1,6 +1,6 @@
 // ajx_kcommon.h — device helpers shared by the kernel translation units (ajx_kernels.hip,
-// ajx_lean.hip): per-device attribute guards, the LDS staging of a ruleset blob, and stage
-// B's outputs (the T bitmap and the And/Or fold of every tree).
+// ajx_lean.hip): per-device attribute guards, the LDS staging of a ruleset blob, the window
+// rings' geometry and the token scanner's stage A for one request. (Stage B: ajx_stageb.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,63 +86,6 @@ __device__ __forceinline__ const uint8_t* stage_blob(const uint8_t* gblob) {
     } else {
         return gblob;
     }
-}
-
-// the And/Or fold of every tree of the ruleset on the pattern bitmaps; a forest ruleset
-// (authjx_compile_forest) writes its n_trees results at r * n_trees + k
-__device__ __forceinline__ void fold_outputs(uint32_t r, const uint8_t* blob, const RulesetHdr* h, const uint64_t t[2],
-                                             const uint64_t u[2], const uint64_t se[2],
-                                             uint8_t* __restrict__ out_tri, int32_t* __restrict__ out_err) {
-    const uint32_t* code = reinterpret_cast<const uint32_t*>(blob + h->off_code);
-    const uint32_t nt = h->pad1[0];
-    if (h->flags & kFlagFlatFold) {  // (one tree, [open, pattern 0, ..., pattern n - 1, close])
-        int32_t ep;
-        out_tri[r] = flat_fold(h, code, t, u, se, &ep);
-        if (out_err) out_err[r] = ep;
-        return;
-    }
-    if (h->flags & kFlagGroupFold) {  // (one tree: groups of patterns under one All / Any)
-        int32_t ep;
-        out_tri[r] = group_fold(h, code, t, u, se, &ep);
-        if (out_err) out_err[r] = ep;
-        return;
-    }
-    if (nt == 0) {
-        int32_t ep;
-        out_tri[r] = run_fold_bits(code, h->n_code, t, u, se, &ep);
-        if (out_err) out_err[r] = ep;
-        return;
-    }
-    const uint32_t* rc = reinterpret_cast<const uint32_t*>(blob + h->pad1[1]);
-    const TreeFold* tf = h->pad1[2] ? reinterpret_cast<const TreeFold*>(blob + h->pad1[2]) : nullptr;
-    for (uint32_t k = 0; k < nt; k++) {
-        int32_t ep;
-        out_tri[(size_t)r * nt + k] = tf && tf[k].shape ? tree_fold(tf[k], t, u, se, &ep)
-                                                        : run_fold_bits(code + rc[2 * k], rc[2 * k + 1], t, u, se, &ep);
-        if (out_err) out_err[(size_t)r * nt + k] = ep;
-    }
-}
-
-// stage B for request r on its capture row: patterns, T bitmap, And/Or fold, outputs.
-// false (nothing written): a value needs the exact scan (a number only ajx_float.h
-// decides), the caller hands the request over
-__device__ __forceinline__ bool finish_request(uint32_t r, const uint8_t* blob, const uint8_t* d, RowRef row,
-                                               uint8_t* __restrict__ out_tri, int32_t* __restrict__ out_err,
-                                               uint64_t* __restrict__ out_bm, uint32_t stride,
-                                               const uint64_t* dec = nullptr, uint8_t* ring = nullptr) {
-    const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
-    uint64_t t[2], u[2];
-    patterns_from_row(blob, d, row, t, u, dec, 0, 1, ring);
-    if ((u[0] & ~h->unsupported[0]) | (u[1] & ~h->unsupported[1])) return false;
-    if (out_bm) {
-        uint64_t* orow = out_bm + (size_t)r * stride;
-        orow[0] = t[0];
-        if (stride > 1) orow[1] = t[1];
-        for (uint32_t w = 2; w < stride; w++) orow[w] = 0ull;
-    }
-    const uint64_t se[2] = {h->static_error[0], h->static_error[1]};
-    fold_outputs(r, blob, h, t, u, se, out_tri, out_err);
-    return true;
 }
 
 // the work-item's 128-B window ring in dynamic LDS: [blob copy (SHARED)] [ring: per wave

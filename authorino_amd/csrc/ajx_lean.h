@@ -34,7 +34,7 @@
 // the first capture of each selector here. Anything else goes to the exact scan
 // (ajx_eval_scan), as with the token scanner of ajx_fast.h.
 //
-// Output: the request's capture row in ajx_fast.h's format (stage B unchanged).
+// Output: the request's capture row (ajx_stageb.h's format, for its stage B).
 #pragma once
 #include "ajx_lean_cls.h"
 
@@ -102,14 +102,20 @@ constexpr uint32_t kIdxKeyLen = kIndexKeyLen;
 
 enum : uint32_t { S_RUN = 0, S_DONE = 1, S_SLOW = 2 };
 
+// the lean scan may take this request (an empty document goes to the exact scan; a capture
+// record holds 24 bits of length)
+AJX_HD bool eligible(const RulesetHdr* h, uint32_t len) {
+    return (h->flags & kFlagFastOk) && len > 0 && len < (1u << 24);
+}
+
 // The walker of one document. ARR: the ruleset has array-index selectors (arrays on
 // selector paths are walked element by element; without, every array is squashed: no
-// selector can match inside one); CAPS: a selector's value can be a container the walk
-// enters (a selector that is a prefix of another). The fewer features, the less state and
-// code per iteration. The lean kernel picks ARR by the ruleset's need (RulesetHdr::lean_feat,
-// kLeanArr) and always runs CAPS = true (launch_lean, ajx_lean.hip: the capture-free
-// instances measured slower); the compiler still records kLeanCaps in lean_feat.
-template <bool ARR = true, bool CAPS = true>
+// selector can match inside one). Without them there is less state and code per iteration;
+// the lean kernel picks ARR by the ruleset's need (RulesetHdr::lean_feat, kLeanArr). Every
+// instance enters captured containers (a selector that is a prefix of another), whether the
+// ruleset needs that or not: capture-free instances measured slower (launch_lean,
+// ajx_lean.hip); the compiler still records kLeanCaps in lean_feat.
+template <bool ARR = true>
 struct Walk {
     // tables
     const TrieNode* tn;
@@ -307,7 +313,7 @@ struct Walk {
         return true;
     }
     AJX_HD void close(uint32_t p) {
-        if (CAPS && ncap) {
+        if (ncap) {
             const uint32_t cs = ncap == 2 ? caps >> 16 : caps & 0xFFFFu, start = ncap == 2 ? cap1s : cap0s;
             if ((cs >> 8) == depth) {
                 row[1 + (cs & 0xFFu)] =
@@ -376,7 +382,7 @@ struct Walk {
         tarr = ARR && arr ? 1u : 0u;
         expk = 1;
         idx = 0;
-        if (CAPS && s >= 0) {
+        if (s >= 0) {
             found |= 1ull << s;  // (first match in document order)
             if (ncap >= 2) { st = S_SLOW; return; }
             const uint32_t v = (uint32_t)s | (depth << 8);  // (s < 64, depth <= 16)
@@ -698,11 +704,11 @@ struct Walk {
 // longer needs: the next window's first half while the current window's first sub-window
 // is walked (the ring keeps the 32 bytes before that sub-window), its second half while
 // the second one is.
-template <int ABL = 0, bool ARR = true, bool CAPS = true, class Loader>
+template <int ABL = 0, bool ARR = true, class Loader>
 AJX_HD bool scan_doc(const uint8_t* blob, uint32_t n, uint32_t mis, RowRef row, uint8_t* ring, Loader& ld,
                      uint64_t dec[2], uint32_t keep = 1) {
     const RulesetHdr* h = (const RulesetHdr*)blob;
-    Walk<ARR, CAPS> w;
+    Walk<ARR> w;
     // the tables as the blob pointer plus uniform offsets: the offsets go to scalar registers
     // and the pointers keep the blob's provenance, so that with the blob staged in LDS every
     // table read is a ds_read (a pointer made uniform through an integer would be generic:
@@ -825,6 +831,15 @@ AJX_HD bool scan_doc(const uint8_t* blob, uint32_t n, uint32_t mis, RowRef row, 
     dec[0] = w.eD;
     dec[1] = w.eT;
     return true;
+}
+// scan_doc as it was spelled while the walker had a second feature parameter (CAPS: captured
+// containers are entered; every instance does that now): a caller that still names it gets
+// the same scan
+template <int ABL, bool ARR, bool CAPS, class Loader>
+AJX_HD bool scan_doc(const uint8_t* blob, uint32_t n, uint32_t mis, RowRef row, uint8_t* ring, Loader& ld,
+                     uint64_t dec[2], uint32_t keep = 1) {
+    static_assert(CAPS, "there is no capture-free walker");
+    return scan_doc<ABL, ARR>(blob, n, mis, row, ring, ld, dec, keep);
 }
 
 // The device loader of scan_doc: LDS-DMA loads of the document's aligned 16-byte blocks

@@ -25,9 +25,9 @@ constexpr uint32_t kLeanMaxBlock = 1024;
 // ajx_unpermute)
 constexpr uint32_t kLeanOutByItem = 2u;
 // ABL: profiling ablations (kernel modes 15..18, lean::scan_doc): stage A cut short, no stage B.
-// FEAT: the walker features of the instance (kLeanArr | kLeanCaps). launch_lean picks by the
-// ruleset's kLeanArr alone (RulesetHdr::lean_feat): every instance it launches has kLeanCaps
-template <bool SHARED, int ABL = 0, int FEAT = 3>
+// ARR: the instance walks arrays on selector paths (lean::Walk). launch_lean picks by the
+// ruleset's kLeanArr (RulesetHdr::lean_feat)
+template <bool SHARED, int ABL = 0, bool ARR = true>
 __global__ __launch_bounds__(AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES) void ajx_scan_lean(
     const uint8_t* const* __restrict__ sets, const uint32_t* __restrict__ set_of_req,
     const uint8_t* __restrict__ arena, const uint64_t* __restrict__ offs, const uint32_t* __restrict__ lens, uint32_t n,
@@ -47,13 +47,12 @@ __global__ __launch_bounds__(AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES) void ajx_scan_le
     const uint8_t* d = arena + offs[r];
     const uint32_t len = lens[r];
     const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
-    bool ok = (h->flags & kFlagFastOk) && len > 0 && len < (1u << 24);  // (empty: the exact scan)
+    bool ok = lean::eligible(h, len);
     uint64_t dec[2] = {0ull, 0ull};
     if (ok) {
         const uint32_t mis = (uint32_t)((uintptr_t)d & 15u);
         lean::DmaLoader ld{reinterpret_cast<const uint4*>(d - mis), (len + mis + 15u) / 16u, wring};
-        ok = lean::scan_doc<ABL, (FEAT & kLeanArr) != 0, (FEAT & kLeanCaps) != 0>(
-            blob, len, mis, row, wring + (threadIdx.x & 63u) * 16u, ld, dec, keep_rows);
+        ok = lean::scan_doc<ABL, ARR>(blob, len, mis, row, wring + (threadIdx.x & 63u) * 16u, ld, dec, keep_rows);
     } else {
         row[0] = kRowSlow;
     }
@@ -81,10 +80,11 @@ hipError_t launch_lean(const Batch& b, const Results& res, const Work& work, con
     const uint32_t abl = plan.abl;
     static std::atomic<uint64_t> attr_done{0};
     hipError_t e = attr_once(attr_done, [] {
-        const void* ks[] = {AJX_LEAN_K(true, 0, 2), AJX_LEAN_K(true, 0, 3), AJX_LEAN_K(false, 0, 3),
+        const void* ks[] = {AJX_LEAN_K(true, 0, false), AJX_LEAN_K(true, 0, true), AJX_LEAN_K(false, 0, true),
 #if defined(AJX_LEAN_ABLATIONS)
-                            AJX_LEAN_K(true, 1, 2), AJX_LEAN_K(true, 2, 2), AJX_LEAN_K(true, 3, 2), AJX_LEAN_K(true, 4, 2),
-                            AJX_LEAN_K(true, 1, 3), AJX_LEAN_K(true, 2, 3), AJX_LEAN_K(true, 3, 3), AJX_LEAN_K(true, 4, 3)
+                            AJX_LEAN_K(true, 1, false), AJX_LEAN_K(true, 2, false), AJX_LEAN_K(true, 3, false),
+                            AJX_LEAN_K(true, 4, false), AJX_LEAN_K(true, 1, true), AJX_LEAN_K(true, 2, true),
+                            AJX_LEAN_K(true, 3, true), AJX_LEAN_K(true, 4, true)
 #endif
         };
         for (const void* k : ks) {
@@ -99,12 +99,12 @@ hipError_t launch_lean(const Batch& b, const Results& res, const Work& work, con
     const uint32_t lgrid = (b.n + lblock - 1) / lblock;
     const RingGeom g = ring_geom(plan.stage_bytes, lblock, lean::kRingBytesPerWave);
     const uint32_t keep = (plan.keep_rows ? kKeepRows : 0u) | (plan.out_k && d_perm ? kLeanOutByItem : 0u);
-    // (two instances, FEAT 2 and 3: without and with array walking, by the ruleset's
-    // kLeanArr. Its kLeanCaps bit is not looked at: both instances enter captured containers,
-    // whether the ruleset needs that or not. The capture-free instances cost the walk loop
-    // scratch reloads of spilled scalar registers, which wait behind the ring's loads in
-    // flight: measured slower, c2 1.39 against 1.27 ms)
-    const uint32_t feat = (plan.lean_feat & kLeanArr) ? 3u : 2u;
+    // (two instances: without and with array walking, by the ruleset's kLeanArr. Its
+    // kLeanCaps bit is not looked at: both instances enter captured containers, whether the
+    // ruleset needs that or not. Capture-free instances cost the walk loop scratch reloads of
+    // spilled scalar registers, which wait behind the ring's loads in flight: measured
+    // slower, c2 1.39 against 1.27 ms)
+    const bool arr = (plan.lean_feat & kLeanArr) != 0;
     using K = void (*)(const uint8_t* const*, const uint32_t*, const uint8_t*, const uint64_t*, const uint32_t*,
                        uint32_t, uint64_t*, uint32_t, uint32_t*, uint32_t*, uint8_t*, int32_t*, uint64_t*, uint32_t,
                        uint32_t, const uint32_t*, uint32_t);
@@ -112,18 +112,17 @@ hipError_t launch_lean(const Batch& b, const Results& res, const Work& work, con
     if (abl) {
 #if defined(AJX_LEAN_ABLATIONS)
         if (!shared || abl > 4) return hipErrorInvalidValue;
-        const bool f2 = feat == 2;
-        k = abl == 1 ? (f2 ? &ajx_scan_lean<true, 1, 2> : &ajx_scan_lean<true, 1, 3>)
-          : abl == 2 ? (f2 ? &ajx_scan_lean<true, 2, 2> : &ajx_scan_lean<true, 2, 3>)
-          : abl == 3 ? (f2 ? &ajx_scan_lean<true, 3, 2> : &ajx_scan_lean<true, 3, 3>)
-                     : (f2 ? &ajx_scan_lean<true, 4, 2> : &ajx_scan_lean<true, 4, 3>);
+        k = abl == 1 ? (arr ? &ajx_scan_lean<true, 1, true> : &ajx_scan_lean<true, 1, false>)
+          : abl == 2 ? (arr ? &ajx_scan_lean<true, 2, true> : &ajx_scan_lean<true, 2, false>)
+          : abl == 3 ? (arr ? &ajx_scan_lean<true, 3, true> : &ajx_scan_lean<true, 3, false>)
+                     : (arr ? &ajx_scan_lean<true, 4, true> : &ajx_scan_lean<true, 4, false>);
 #else
         return hipErrorInvalidValue;  // (a profiling build: scripts/build_variant.sh NAME -DAJX_LEAN_ABLATIONS)
 #endif
     } else if (!shared) {
-        k = &ajx_scan_lean<false, 0, 3>;
+        k = &ajx_scan_lean<false, 0, true>;
     } else {
-        k = feat == 2 ? &ajx_scan_lean<true, 0, 2> : &ajx_scan_lean<true, 0, 3>;
+        k = arr ? &ajx_scan_lean<true, 0, true> : &ajx_scan_lean<true, 0, false>;
     }
     hipLaunchKernelGGL(k, dim3(lgrid), dim3(lblock), g.lds, stream, b.sets, nullptr, b.arena, b.offs, b.lens, b.n,
                        work.rows, work.row_stride, work.slow_count, work.slow_ids, res.tri, res.err, res.bm,
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(kFastBlock, AJX_FAST_WAVES) void ajx_scan_fused_ten
             const uint32_t len = lens[r];
             const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
             uint64_t dec[2] = {0ull, 0ull};
-            bool ok = (h->flags & kFlagFastOk) && len > 0 && len < (1u << 24);
+            bool ok = lean::eligible(h, len);
             if (ok) {
                 uint8_t* wring = reinterpret_cast<uint8_t*>(s_stage) + ring_off + wv * lean::kRingBytesPerWave;
                 const uint32_t mis = (uint32_t)((uintptr_t)d & 15u);

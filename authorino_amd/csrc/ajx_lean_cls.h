@@ -3,7 +3,7 @@
 // grammar on 32-bit masks), shared by the lean walker (ajx_lean.h) and the streaming
 // kernel (ajx_stream.h). See ajx_lean.h for the scan it serves.
 #pragma once
-#include "ajx_fast.h"
+#include "ajx_stageb.h"
 
 namespace ajx {
 namespace lean {

@@ -37,7 +37,7 @@
 // its first byte opens the root container, the root closes inside it, and no check fails
 // before that close; everything else goes to the exact scan.
 //
-// After the span, each lane runs stage B (ajx_fast.h patterns_from_row) for one document
+// After the span, each lane runs stage B (ajx_stageb.h patterns_from_row) for one document
 // of the span on its LDS capture row.
 #pragma once
 #include "ajx_lean_cls.h"
@@ -58,7 +58,7 @@ constexpr uint32_t kWinBytes = kWinBlocks * 32u;
 constexpr uint32_t kMaxLevel = 16;             // container nesting tracked (deeper: exact scan)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kMaxLen = (1u << 23) - 2u;  // longer documents: exact scan
-// capture record (the row format of ajx_fast.h) with its end still open: stage B finds it
+// capture record (the row format of ajx_stageb.h) with its end still open: stage B finds it
 constexpr uint32_t kOpenEnd = 1u << 28;
 constexpr uint32_t kTypeUnknown = 7u;
 
@@ -1000,35 +1000,87 @@ AJX_HD bool finish_light(uint32_t r, const uint8_t* blob, const Tabs& T, const u
     const uint64_t want = np >= 64 ? ~0ull : (1ull << np) - 1ull;
     if ((all & want) != want) return false;
     const uint64_t t[2] = {t0 & want, 0ull}, u[2] = {0ull, 0ull}, se[2] = {0ull, 0ull};
-    if (out_bm) {
-        uint64_t* orow = out_bm + (size_t)r * stride;
-        orow[0] = t[0];
-        for (uint32_t w = 1; w < stride; w++) orow[w] = 0ull;
-    }
+    write_bitmap(r, t, out_bm, stride);
+    fold_outputs(r, blob, h, t, u, se, out_tri, out_err);
+    return true;
+}
+
+// fold_outputs (ajx_stageb.h) by the 64 lanes of a wave that share request r (t / u / se the
+// same on every lane): every lane runs the (uniform) fold, its code words handed out from
+// registers (64 per coalesced read) instead of one dependent memory read each, and lane 0
+// stores the results.
+AJX_HD void fold_outputs_wave(uint32_t r, const uint8_t* blob, const RulesetHdr* h, const uint64_t t[2],
+                              const uint64_t u[2], const uint64_t se[2], uint8_t* __restrict__ out_tri,
+                              int32_t* __restrict__ out_err) {
+    const uint32_t lane = wave::lane();
     const uint32_t* code = reinterpret_cast<const uint32_t*>(blob + h->off_code);
     const uint32_t nt = h->pad1[0];
+    auto fold = [&](const uint32_t* c, uint32_t nc, int32_t* ep) -> uint8_t {
+        // (one tree whose fold reads off the bitmaps: kFlagGroupFold)
+        if (c == code && nt == 0 && (h->flags & kFlagGroupFold)) return group_fold(h, code, t, u, se, ep);
+        // a flat All / Any (open, patterns, close; up to 64 words): the lanes hold one
+        // word each and the result is the first leaf, in code order, that is not the
+        // group's identity (the interpreter's sticky value), else the identity
+        if (nc >= 3 && nc <= 64) {
+            const uint32_t cw = lane < nc ? c[lane] : 0u;
+            const uint32_t op0 = wave::readlane(cw, 0) >> 24, opl = wave::readlane(cw, nc - 1u) >> 24;
+            const bool leaf = lane >= 1 && lane + 1u < nc;
+            const uint64_t leaves = wave::ballot(leaf), pats = wave::ballot(leaf && (cw >> 24) == C_PAT);
+            if ((op0 == C_OPEN_AND || op0 == C_OPEN_OR) && opl == C_CLOSE && pats == leaves) {
+                const uint32_t arg = cw & 0xFFFFFFu, q = arg >> 6;
+                const uint64_t bit = 1ull << (arg & 63u);
+                const uint32_t v = ((q ? se[1] : se[0]) & bit)  ? (uint32_t)V_E
+                                   : ((q ? u[1] : u[0]) & bit) ? (uint32_t)V_U
+                                   : ((q ? t[1] : t[0]) & bit) ? (uint32_t)V_T
+                                                                : (uint32_t)V_F;
+                const uint32_t ident = op0 == C_OPEN_OR ? (uint32_t)V_F : (uint32_t)V_T;
+                const uint64_t stick = wave::ballot(leaf && v != ident);
+                if (!stick) {
+                    *ep = -1;
+                    return (uint8_t)ident;
+                }
+                const uint32_t k = (uint32_t)__builtin_ctzll(stick);
+                const uint32_t vk = wave::readlane(v, k), ak = wave::readlane(arg, k);
+                *ep = (vk == V_E || vk == V_U) ? (int32_t)ak : -1;
+                return (uint8_t)vk;
+            }
+        }
+        uint32_t creg = 0, cbase = 0xFFFFFFFFu;
+        return run_fold_bits_f(
+            [&](uint32_t k) -> uint32_t {
+                const uint32_t b = k & ~63u;
+                if (b != cbase) {
+                    cbase = b;
+                    creg = b + lane < nc ? c[b + lane] : 0u;
+                }
+                return wave::readlane(creg, k & 63u);
+            },
+            nc, t, u, se, ep);
+    };
     if (nt == 0) {
         int32_t ep;
-        out_tri[r] = (h->flags & kFlagFlatFold)    ? flat_fold(h, code, t, u, se, &ep)
-                     : (h->flags & kFlagGroupFold) ? group_fold(h, code, t, u, se, &ep)
-                                                   : run_fold_bits(code, h->n_code, t, u, se, &ep);
-        if (out_err) out_err[r] = ep;
-        return true;
+        const uint8_t v = fold(code, h->n_code, &ep);
+        if (lane == 0) {
+            out_tri[r] = v;
+            if (out_err) out_err[r] = ep;
+        }
+        return;
     }
     const uint32_t* rc = reinterpret_cast<const uint32_t*>(blob + h->pad1[1]);
     const TreeFold* tf = h->pad1[2] ? reinterpret_cast<const TreeFold*>(blob + h->pad1[2]) : nullptr;
     for (uint32_t k = 0; k < nt; k++) {
         int32_t ep;
-        out_tri[(size_t)r * nt + k] = tf && tf[k].shape ? tree_fold(tf[k], t, u, se, &ep)
-                                                        : run_fold_bits(code + rc[2 * k], rc[2 * k + 1], t, u, se, &ep);
-        if (out_err) out_err[(size_t)r * nt + k] = ep;
+        const uint8_t v = tf && tf[k].shape ? tree_fold(tf[k], t, u, se, &ep) : fold(code + rc[2 * k], rc[2 * k + 1], &ep);
+        if (lane == 0) {
+            out_tri[(size_t)r * nt + k] = v;
+            if (out_err) out_err[(size_t)r * nt + k] = ep;
+        }
     }
-    return true;
 }
 
 // Stage B for a request the stream did not decide (ajx_stream_finish, one work-item per
 // request; its row in HBM: found word, records, the 4 eager words): the open values from
-// the document, the arrays' decisions, ajx_fast.h's patterns_from_row, the T bitmap and the
+// the document, the arrays' decisions, ajx_stageb.h's patterns_from_row, the T bitmap and the
 // fold. false: the exact scan decides the request (the row is marked kRowSlow).
 // dwp: the eager words (null: they follow the row's records, as in the stage-B rows).
 // WAVE: all 64 lanes of a wave share the one request (the row in LDS): lane l resolves the
@@ -1145,78 +1197,33 @@ AJX_HD bool finish_full(uint32_t r, const uint8_t* blob, const uint8_t* d, uint3
         if (lane == 0) row[0] = kRowSlow;
         return false;
     }
-    if (lane == 0 && out_bm) {
-        uint64_t* orow = out_bm + (size_t)r * stride;
-        orow[0] = t[0];
-        if (stride > 1) orow[1] = t[1];
-        for (uint32_t w = 2; w < stride; w++) orow[w] = 0ull;
-    }
+    if (lane == 0) write_bitmap(r, t, out_bm, stride);
     const uint64_t se[2] = {h->static_error[0], h->static_error[1]};
-    const uint32_t* code = reinterpret_cast<const uint32_t*>(blob + h->off_code);
-    const uint32_t nt = h->pad1[0];
-    // WAVE: every lane runs the (uniform) fold, its code words handed out from registers
-    // (64 per coalesced read) instead of one dependent memory read each
-    auto fold = [&](const uint32_t* c, uint32_t nc, int32_t* ep) -> uint8_t {
-        // (one tree whose fold reads off the bitmaps: kFlagFlatFold / kFlagGroupFold)
-        if (c == code && nt == 0 && (h->flags & kFlagGroupFold)) return group_fold(h, code, t, u, se, ep);
-        if (!WAVE && c == code && nt == 0 && (h->flags & kFlagFlatFold)) return flat_fold(h, code, t, u, se, ep);
-        if constexpr (WAVE) {
-            // a flat All / Any (open, patterns, close; up to 64 words): the lanes hold one
-            // word each and the result is the first leaf, in code order, that is not the
-            // group's identity (the interpreter's sticky value), else the identity
-            if (nc >= 3 && nc <= 64) {
-                const uint32_t cw = lane < nc ? c[lane] : 0u;
-                const uint32_t op0 = wave::readlane(cw, 0) >> 24, opl = wave::readlane(cw, nc - 1u) >> 24;
-                const bool leaf = lane >= 1 && lane + 1u < nc;
-                const uint64_t leaves = wave::ballot(leaf), pats = wave::ballot(leaf && (cw >> 24) == C_PAT);
-                if ((op0 == C_OPEN_AND || op0 == C_OPEN_OR) && opl == C_CLOSE && pats == leaves) {
-                    const uint32_t arg = cw & 0xFFFFFFu, q = arg >> 6;
-                    const uint64_t bit = 1ull << (arg & 63u);
-                    const uint32_t v = ((q ? se[1] : se[0]) & bit)  ? (uint32_t)V_E
-                                       : ((q ? u[1] : u[0]) & bit) ? (uint32_t)V_U
-                                       : ((q ? t[1] : t[0]) & bit) ? (uint32_t)V_T
-                                                                    : (uint32_t)V_F;
-                    const uint32_t ident = op0 == C_OPEN_OR ? (uint32_t)V_F : (uint32_t)V_T;
-                    const uint64_t stick = wave::ballot(leaf && v != ident);
-                    if (!stick) {
-                        *ep = -1;
-                        return (uint8_t)ident;
-                    }
-                    const uint32_t k = (uint32_t)__builtin_ctzll(stick);
-                    const uint32_t vk = wave::readlane(v, k), ak = wave::readlane(arg, k);
-                    *ep = (vk == V_E || vk == V_U) ? (int32_t)ak : -1;
-                    return (uint8_t)vk;
-                }
-            }
-            uint32_t creg = 0, cbase = 0xFFFFFFFFu;
-            return run_fold_bits_f(
-                [&](uint32_t k) -> uint32_t {
-                    const uint32_t b = k & ~63u;
-                    if (b != cbase) {
-                        cbase = b;
-                        creg = b + lane < nc ? c[b + lane] : 0u;
-                    }
-                    return wave::readlane(creg, k & 63u);
-                },
-                nc, t, u, se, ep);
-        }
-        return run_fold_bits(c, nc, t, u, se, ep);
-    };
-    if (nt == 0) {
-        int32_t ep;
-        const uint8_t v = fold(code, h->n_code, &ep);
-        if (lane == 0) {
+    if constexpr (WAVE) {
+        fold_outputs_wave(r, blob, h, t, u, se, out_tri, out_err);
+    } else {
+        // fold_outputs' dispatch in this function's own words, and the only other copy of it:
+        // with the call, ajx_stream_finish<false, 0> spills 143 scalar registers against 140
+        // (DESIGN §5.12); with this text ajx_stream_finish's instances compile as before
+        const uint32_t* code = reinterpret_cast<const uint32_t*>(blob + h->off_code);
+        const uint32_t nt = h->pad1[0];
+        auto fold = [&](const uint32_t* c, uint32_t nc, int32_t* ep) -> uint8_t {
+            if (c == code && nt == 0 && (h->flags & kFlagGroupFold)) return group_fold(h, code, t, u, se, ep);
+            if (c == code && nt == 0 && (h->flags & kFlagFlatFold)) return flat_fold(h, code, t, u, se, ep);
+            return run_fold_bits(c, nc, t, u, se, ep);
+        };
+        if (nt == 0) {
+            int32_t ep;
+            const uint8_t v = fold(code, h->n_code, &ep);
             out_tri[r] = v;
             if (out_err) out_err[r] = ep;
+            return true;
         }
-        return true;
-    }
-    const uint32_t* rc = reinterpret_cast<const uint32_t*>(blob + h->pad1[1]);
-    const TreeFold* tf = h->pad1[2] ? reinterpret_cast<const TreeFold*>(blob + h->pad1[2]) : nullptr;
-    for (uint32_t k = 0; k < nt; k++) {
-        int32_t ep;
-        const uint8_t v = tf && tf[k].shape ? tree_fold(tf[k], t, u, se, &ep) : fold(code + rc[2 * k], rc[2 * k + 1], &ep);
-        if (lane == 0) {
+        const uint32_t* rc = reinterpret_cast<const uint32_t*>(blob + h->pad1[1]);
+        const TreeFold* tf = h->pad1[2] ? reinterpret_cast<const TreeFold*>(blob + h->pad1[2]) : nullptr;
+        for (uint32_t k = 0; k < nt; k++) {
+            int32_t ep;
+            const uint8_t v = tf && tf[k].shape ? tree_fold(tf[k], t, u, se, &ep) : fold(code + rc[2 * k], rc[2 * k + 1], &ep);
             out_tri[(size_t)r * nt + k] = v;
             if (out_err) out_err[(size_t)r * nt + k] = ep;
         }

@@ -211,6 +211,47 @@ int ht_regex_match(void* dv, const uint8_t* s, uint32_t n) {
 
 }  // extern "C"
 
+static uint64_t g_flat_folds = 0;  // (lean evaluations whose ruleset took the flat fold)
+extern "C" uint64_t ht_flat_folds() { return g_flat_folds; }
+static uint64_t g_group_folds = 0;  // (the same for the group fold)
+extern "C" uint64_t ht_group_folds() { return g_group_folds; }
+
+// Stage B as the kernels run it (finish_request, ajx_stageb.h) for one request on its capture
+// row; dec / ring: the lean scan's decisions and the lane's span buffer, as its kernel passes
+// them. res[p] is read back from what it wrote (static E, unsupported, the T bitmap). Returns
+// -1 when it hands the request to the exact scan; 99 (no tri-state: the test's comparison
+// fails) when a tree's result is not the code interpreter's on res, or a bitmap word past the
+// ruleset's two was not zeroed; else the interpreter's tri-state of the fold code.
+static int stage_b(const uint8_t* blob, const uint8_t* d, uint64_t* row, const uint64_t* dec, uint8_t* ring,
+                   uint8_t* res, int32_t* err, bool count) {
+    const RulesetHdr* hd = (const RulesetHdr*)blob;
+    const uint32_t nt = hd->pad1[0], slots = nt ? nt : 1u;
+    constexpr uint32_t kStride = 4;  // (the ruleset's two words and two the writer must zero)
+    uint64_t bm[kStride];
+    std::memset(bm, 0xFF, sizeof bm);
+    std::vector<uint8_t> tri(slots, 0xEE);
+    std::vector<int32_t> ep(slots, -7);
+    if (!finish_request(0, blob, d, RowRef(row), tri.data(), ep.data(), bm, kStride, dec, ring)) return -1;
+    if (bm[2] | bm[3]) return 99;
+    for (uint32_t p = 0; p < hd->n_patterns; p++) {
+        const uint64_t bit = 1ull << (p & 63);
+        const uint32_t k = p >> 6;
+        res[p] = (hd->static_error[k] & bit) ? V_E : (hd->unsupported[k] & bit) ? V_U : (bm[k] & bit) ? V_T : V_F;
+    }
+    if (count && (hd->flags & kFlagFlatFold)) g_flat_folds++;
+    if (count && (hd->flags & kFlagGroupFold)) g_group_folds++;
+    const uint32_t* code = (const uint32_t*)(blob + hd->off_code);
+    const auto rp = [&](uint32_t p) { return res[p]; };
+    const int whole = run_fold(code, hd->n_code, rp, err);
+    if (nt == 0) return tri[0] == whole && ep[0] == *err ? whole : 99;
+    const uint32_t* rc = (const uint32_t*)(blob + hd->pad1[1]);
+    for (uint32_t k = 0; k < nt; k++) {  // (a forest: tree by tree)
+        int32_t e;
+        if (tri[k] != run_fold(code + rc[2 * k], rc[2 * k + 1], rp, &e) || ep[k] != e) return 99;
+    }
+    return whole;
+}
+
 extern "C" {
 // single-pass path: returns -1 when the document is handed to the exact scan, else the
 // tri-state; res[p] receives each pattern's value. `mis` places the copy at that
@@ -247,16 +288,7 @@ static int eval_single_pass(void* h, const uint8_t* doc, uint32_t len, uint32_t 
     const bool ok = scan_doc(blob, blob_tables(blob), d, len, row.data(), ring, load);
     if (!ok) return -1;
     if (row_out) std::memcpy(row_out, row.data(), row.size() * sizeof(uint64_t));
-    uint64_t t[2], u[2];
-    patterns_from_row(blob, d, row.data(), t, u);
-    if ((u[0] & ~hd->unsupported[0]) | (u[1] & ~hd->unsupported[1])) return -1;  // a number for the exact scan
-    const uint32_t* code = (const uint32_t*)(blob + hd->off_code);
-    for (uint32_t p = 0; p < hd->n_patterns; p++) {
-        uint64_t bit = 1ull << (p & 63);
-        uint32_t k = p >> 6;
-        res[p] = (hd->static_error[k] & bit) ? V_E : (u[k] & bit) ? V_U : (t[k] & bit) ? V_T : V_F;
-    }
-    return run_fold(code, hd->n_code, [&](uint32_t p) { return res[p]; }, err);
+    return stage_b(blob, d, row.data(), nullptr, nullptr, res, err, false);
 }
 }
 
@@ -287,16 +319,12 @@ extern "C" void ht_lean_last_dec(uint64_t* out) {
 // default when no caller reads the rows); 1 every record
 static uint32_t g_lean_keep = 1;
 extern "C" void ht_lean_keep(int keep) { g_lean_keep = keep ? 1u : 0u; }
-static uint64_t g_flat_folds = 0;  // (lean evaluations whose ruleset took the flat fold)
-extern "C" uint64_t ht_flat_folds() { return g_flat_folds; }
-static uint64_t g_group_folds = 0;  // (the same for the group fold)
-extern "C" uint64_t ht_group_folds() { return g_group_folds; }
 extern "C" int ht_eval_lean_row(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err,
                                 uint64_t* row_out) {
     const uint8_t* blob = ((HtRuleset*)h)->c.blob.data();
     const RulesetHdr* hd = (const RulesetHdr*)blob;
     if (!(hd->flags & kFlagFastOk)) return -2;
-    if (len == 0) return -1;  // (the kernels send empty documents to the exact scan)
+    if (!lean::eligible(hd, len)) return -1;  // (as the kernels: empty or too long, the exact scan)
     std::vector<uint8_t> buf(len + 96, 0x7A);  // (neighbour bytes around the document)
     uintptr_t base = ((uintptr_t)buf.data() + 15) & ~(uintptr_t)15;
     uint8_t* d = (uint8_t*)base + (mis & 15);
@@ -311,39 +339,16 @@ extern "C" int ht_eval_lean_row(void* h, const uint8_t* doc, uint32_t len, uint3
     lean::CopyLoader ld{(const uint8_t*)a, nblk, nb, ring_mem.data() + ((mis * 5u) & 63u) * 16u};
     uint64_t dec[2] = {0, 0};
     // (the instance the kernel takes for this ruleset: RulesetHdr::lean_feat)
-    const uint32_t m15 = (uint32_t)(mis & 15), f = (hd->lean_feat & kLeanArr) ? 3u : 2u;
+    const uint32_t m15 = (uint32_t)(mis & 15);
     const RowRef rr(row.data());
-    const bool ok = f == 2 ? lean::scan_doc<0, false, true>(blob, len, m15, rr, ld.lane_ring, ld, dec, g_lean_keep)
-                           : lean::scan_doc<0, true, true>(blob, len, m15, rr, ld.lane_ring, ld, dec, g_lean_keep);
+    const bool ok = (hd->lean_feat & kLeanArr) ? lean::scan_doc<0, true>(blob, len, m15, rr, ld.lane_ring, ld, dec, g_lean_keep)
+                                               : lean::scan_doc<0, false>(blob, len, m15, rr, ld.lane_ring, ld, dec, g_lean_keep);
     g_last_dec[0] = dec[0];
     g_last_dec[1] = dec[1];
     if (!ok) return -1;
     if (row_out) std::memcpy(row_out, row.data(), row.size() * sizeof(uint64_t));
-    uint64_t t[2], u[2];
-    patterns_from_row(blob, d, row.data(), t, u, dec, 0, 1, ld.lane_ring);  // (values from the lane's buffer, as the kernel)
-    if ((u[0] & ~hd->unsupported[0]) | (u[1] & ~hd->unsupported[1])) return -1;
-    const uint32_t* code = (const uint32_t*)(blob + hd->off_code);
-    for (uint32_t p = 0; p < hd->n_patterns; p++) {
-        uint64_t bit = 1ull << (p & 63);
-        uint32_t k = p >> 6;
-        res[p] = (hd->static_error[k] & bit) ? V_E : (u[k] & bit) ? V_U : (t[k] & bit) ? V_T : V_F;
-    }
-    const int tri = run_fold(code, hd->n_code, [&](uint32_t p) { return res[p]; }, err);
-    if (hd->flags & kFlagFlatFold) {  // (the kernels' fold for such rulesets: it must agree)
-        const uint64_t se[2] = {hd->static_error[0], hd->static_error[1]};
-        int32_t fe;
-        const uint8_t ft = flat_fold(hd, code, t, u, se, &fe);
-        g_flat_folds++;
-        if (ft != tri || fe != *err) return 99;  // (no tri-state: the test's comparison fails)
-    }
-    if (hd->flags & kFlagGroupFold) {
-        const uint64_t se[2] = {hd->static_error[0], hd->static_error[1]};
-        int32_t fe;
-        const uint8_t ft = group_fold(hd, code, t, u, se, &fe);
-        g_group_folds++;
-        if (ft != tri || fe != *err) return 99;
-    }
-    return tri;
+    // (values from the lane's span buffer, as the kernel)
+    return stage_b(blob, d, row.data(), dec, ld.lane_ring, res, err, true);
 }
 // tree_fold against the code interpreter for every forest tree with a TreeFold shape, on n
 // random 128-bit (T, U, static E) bitmaps: the number of differences (-1: no such tree)
