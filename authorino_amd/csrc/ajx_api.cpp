@@ -71,17 +71,16 @@ struct Workspace {
     hipEvent_t sets_ev[2] = {nullptr, nullptr};
     bool sets_ev_rec[2] = {false, false};
     std::vector<const uint8_t*> last_sets;
-    // [0] = count, [1..] = ids: requests for the exact scan (the streaming kernel: [1] its
-    // stage-B count, [2] its finished waves, ids from [3])
+    // [0] = count, [1..] = ids: requests for the exact scan (the streaming kernel: its
+    // ajx::StreamCounters, the ids after them)
     uint32_t* d_slow = nullptr;
     uint32_t slow_cap = 0;
-    // the streaming kernel's small-batch instance (FIN) leaves [0..2] zero for the next launch
-    // on this stream (no fill) and publishes its exact-path count at [3]
-    bool cnt_zero = false, exact3 = false;
+    // the streaming kernel's small-batch instance (FIN) leaves its counters zero for the next
+    // launch on this stream (no fill) and publishes its exact-path count (exact_published)
+    bool cnt_zero = false, exact_published = false;
     uint64_t* d_rows = nullptr;  // stage-A capture rows
     size_t rows_cap = 0;         // in u64
-    // length-bucketed request order: perm [n] | histogram (2 x 1024 + 1 u32, in 4096) |
-    // pos_of [n] (each request's work-item)
+    // length-bucketed request order and the streaming kernel's stage-B list (ajx::PermBuf)
     uint32_t* d_perm = nullptr;
     uint32_t perm_cap = 0;
     uint8_t* d_tout = nullptr;  // the lean kernel's outputs in work-item order (tout_bytes)
@@ -282,15 +281,15 @@ int ensure_work(Workspace* w, uint32_t n, uint32_t row_stride) {
         if (w->d_slow) (void)hipFree(w->d_slow);
         w->d_slow = nullptr;
         w->slow_cap = 0;
-        HIP_OK(hipMalloc(&w->d_slow, ((size_t)n + 4) * sizeof(uint32_t)));
+        HIP_OK(hipMalloc(&w->d_slow, ((size_t)n + ajx::kStreamCounterWords) * sizeof(uint32_t)));
         w->slow_cap = n;
-        w->cnt_zero = w->exact3 = false;
+        w->cnt_zero = w->exact_published = false;
     }
     if (n > w->perm_cap) {
         if (w->d_perm) (void)hipFree(w->d_perm);
         w->d_perm = nullptr;
         w->perm_cap = 0;
-        HIP_OK(hipMalloc(&w->d_perm, (2 * (size_t)n + 4096) * sizeof(uint32_t)));
+        HIP_OK(hipMalloc(&w->d_perm, ajx::PermBuf::words(n) * sizeof(uint32_t)));
         w->perm_cap = n;
     }
     if (rows_need > w->rows_cap) {
@@ -580,28 +579,30 @@ static int eval_device(authjx_ctx* ctx, const authjx_ruleset* const* sets, uint3
     w->rows_wave = true;
     // (the counters are zero only after a FIN launch: every other launch fills them itself)
     bool cnt_zero = w->cnt_zero;
-    w->cnt_zero = w->exact3 = false;
+    w->cnt_zero = w->exact_published = false;
     const ajx::Batch batch{w->d_sets, d_set_of_req, d_arena, d_offs, d_lens, n};
     const ajx::Results res{d_out_tristate, d_out_err_idx, d_out_bitmap, bitmap_stride_words};
     if (plan.path == ajx::kPathExact) {
         HIP_OK(ajx::launch_eval_scan(batch, res, plan.mods != 0, s));
     } else if (plan.path == ajx::kPathStream) {
-        // the streaming kernel (ajx_stream.h), its stage B over the d_perm buffer as the
-        // stage-B list; the slow ids after its three counters
-        const ajx::Work work{w->d_rows, plan.rows_stride, w->d_slow, w->d_slow + 3};
-        HIP_OK(ajx::launch_eval_stream(batch, res, work, plan, in.max_blob, in.max_rec, w->d_perm, &cnt_zero, s));
-        w->cnt_zero = w->exact3 = cnt_zero;
+        // the streaming kernel (ajx_stream.h), its stage B over the order buffer as the
+        // stage-B list; the slow ids after its counters
+        const ajx::Work work{w->d_rows, plan.rows_stride, w->d_slow, ajx::stream_slow_ids(w->d_slow)};
+        HIP_OK(ajx::launch_eval_stream(batch, res, work, plan, in.max_blob, in.max_rec, ajx::PermBuf{w->d_perm, n}.stage_list(),
+                                       &cnt_zero, s));
+        w->cnt_zero = w->exact_published = cnt_zero;
     } else {
         const uint32_t* perm = nullptr;
         uint32_t* pos_of = nullptr;
+        const ajx::PermBuf order{w->d_perm, n};
         if (plan.len_order) {
             if (plan.want_pos_of) {
                 rc = ensure_tout(w, ajx::tout_bytes(n, plan.n_out, plan.tout_bm ? bitmap_stride_words : 0u));
                 if (rc != AUTHJX_OK) return rc;
-                pos_of = w->d_perm + (size_t)n + 4096;
+                pos_of = order.pos_of();
             }
-            HIP_OK(ajx::launch_len_order(d_lens, n, w->d_perm + n, w->d_perm, pos_of, s));
-            perm = w->d_perm;
+            HIP_OK(ajx::launch_len_order(d_lens, n, order.hist(), order.perm(), pos_of, s));
+            perm = order.perm();
         }
         w->rows_perm = perm;
         const ajx::Work work{w->d_rows, plan.rows_stride, w->d_slow, w->d_slow + 1};
@@ -658,12 +659,13 @@ int authjx_select_text_batch_device(authjx_ctx* ctx, const authjx_ruleset* const
     if (rc != AUTHJX_OK) return rc;
     const bool exact = force_scan != 0;  // the exact Get per selector (cross-check)
     w->rows_rs = nullptr;  // (the rows are rewritten for this ruleset)
-    w->cnt_zero = w->exact3 = false;  // (its slow count is filled and left nonzero)
+    w->cnt_zero = w->exact_published = false;  // (its slow count is filled and left nonzero)
     if (!exact && (rc = ensure_work(w, n, row_stride)) != AUTHJX_OK) return rc;
     const uint32_t* perm = nullptr;
     if (!exact && len_sort && n_sets == 1 && n >= 4096) {
-        HIP_OK(ajx::launch_len_order(d_lens, n, w->d_perm + n, w->d_perm, nullptr, s));
-        perm = w->d_perm;
+        const ajx::PermBuf order{w->d_perm, n};
+        HIP_OK(ajx::launch_len_order(d_lens, n, order.hist(), order.perm(), nullptr, s));
+        perm = order.perm();
     }
     const uint32_t shared_bytes =
         (n_sets == 1 && sets[0]->c.blob.size() <= ajx::kMaxSharedBlobBytes) ? (uint32_t)sets[0]->c.blob.size() : 0u;
@@ -831,7 +833,8 @@ int64_t authjx_last_exact_count(authjx_ctx* ctx) {
     if (!w->d_slow || !w->ran) return -1;
     uint32_t c = 0;
     if (hipSetDevice(ctx->device) != hipSuccess || hipEventSynchronize(w->ev1) != hipSuccess ||
-        hipMemcpy(&c, w->d_slow + (w->exact3 ? 3 : 0), sizeof c, hipMemcpyDeviceToHost) != hipSuccess)
+        hipMemcpy(&c, w->exact_published ? &ajx::stream_counters(w->d_slow)->exact_published : w->d_slow, sizeof c,
+                  hipMemcpyDeviceToHost) != hipSuccess)
         return AUTHJX_EDEVICE;
     return (int64_t)c;
 }

@@ -1,12 +1,12 @@
 // ajx_kcommon.h — device helpers shared by the kernel translation units (ajx_kernels.hip,
 // ajx_lean.hip): per-device attribute guards, the LDS staging of a ruleset blob, the window
-// rings' geometry and the token scanner's stage A for one request. (Stage B: ajx_stageb.h.)
+// rings' geometry. (The per-request bodies: ajx_request.h; stage B: ajx_stageb.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 
-#include "ajx_fast.h"
+#include "ajx_request.h"
 
 #ifndef AJX_FAST_WAVES
 #define AJX_FAST_WAVES 4  // waves per SIMD the single-pass kernels' register budget is set for
@@ -55,23 +55,6 @@ __device__ __forceinline__ void copy_words(uint4* __restrict__ dst, const uint4*
         if (k1 < nq) dst[k1] = v1;
         if (k2 < nq) dst[k2] = v2;
         if (k3 < nq) dst[k3] = v3;
-    }
-}
-
-// copy_words with every load unconditional (past the end, word b again): the array stays
-// in registers (the streaming kernel's per-wave blob copy: c4 serving 7.8 k -> 4.0 k clocks)
-__device__ __forceinline__ void copy_words_reg(uint4* __restrict__ dst, const uint4* __restrict__ src, uint32_t nq,
-                                               uint32_t t, uint32_t nt) {
-    for (uint32_t b = t; b < nq; b += 8u * nt) {
-        uint4 v[8];
-#pragma unroll
-        for (uint32_t j = 0; j < 8; j++) {
-            const uint32_t k = b + j * nt;
-            v[j] = src[k < nq ? k : b];
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < 8; j++)
-            if (b + j * nt < nq) dst[b + j * nt] = v[j];
     }
 }
 
@@ -127,9 +110,6 @@ static inline uint32_t staged_block(uint32_t blob_bytes, uint32_t max_block, uin
 static inline uint32_t fast_block(uint32_t blob_bytes) {
     return staged_block(blob_bytes, kFastMaxBlock, AJX_FAST_WAVES, kWinRingBytesPerWave);
 }
-// keep_rows (the stream and lean kernels' parameter), bit 0: every request's capture row is
-// written, for authjx_select_from_eval_device. Each kernel names its own bit 1.
-constexpr uint32_t kKeepRows = 1u;
 __device__ __forceinline__ WinRing lane_ring(uint32_t ring_off) {
     extern __shared__ uint4 s_dyn_ring[];
     WinRing r;
@@ -137,25 +117,6 @@ __device__ __forceinline__ WinRing lane_ring(uint32_t ring_off) {
     r.lane16 = (threadIdx.x & 63u) * 16u;
     r.cstride = 64u * 16u;
     return r;
-}
-
-// stage A for request r: single-pass scan into its capture row (false: slow list)
-__device__ __forceinline__ bool scan_request(const uint8_t* blob, const uint8_t* d, uint32_t len, RowRef row,
-                                             const WinRing& ring) {
-    const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
-    if (!(h->flags & kFlagFastOk) || len >= (1u << 24)) {
-        row[0] = kRowSlow;
-        return false;
-    }
-    const uint4* a4 = reinterpret_cast<const uint4*>(d - ((uintptr_t)d & 15u));
-    auto load = [&](uint32_t b, uint32_t nblk) -> Block16 {
-        if (b < nblk) {
-            const uint4 v = a4[b];
-            return Block16{v.x, v.y, v.z, v.w};
-        }
-        return Block16{0u, 0u, 0u, 0u};
-    };
-    return scan_doc(blob, blob_tables(blob), d, len, row, ring, load);
 }
 
 }  // namespace ajx

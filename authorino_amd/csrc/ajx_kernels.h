@@ -101,10 +101,10 @@ hipError_t launch_tenant(const Batch& b, const Results& res, const Work& work, c
 // stream-eligible): one request per wave under its own ruleset, tables from global memory,
 // blob_bytes and n_rec the batch's largest. work.rows: rows of row_stride >= 5 + n_rec words
 // for n requests (wave layout, work-item = request): the rows stage B reads, and with
-// plan.keep_rows every request's row. d_stage_ids: n u32; work.slow_count[1] (the stage-B
-// count) and [2] (finished waves) follow the slow count. counters_zero (in): [0..2] are
-// zero already, no fill; (out): this launch leaves them zero (the small-batch instance: its
-// last wave clears them, the slow count moved to [3]). Of the plan: stream_mode, per
+// plan.keep_rows every request's row. d_stage_ids: n u32; work.slow_count: the path's
+// StreamCounters (ajx_plan.h), work.slow_ids after them. counters_zero (in): the counters
+// are zero already, no fill; (out): this launch leaves them zero (the small-batch instance:
+// its last wave clears them, the slow count kept in exact_published). Of the plan: stream_mode, per
 // (requests per wave, 1..32: fewer for small batches, so more waves share the walk), mods.
 bool stream_eligible(const uint8_t* host_blob, uint32_t blob_bytes);
 // capture records of the streaming kernel's rows (n_selectors + exact selectors' prefixes)

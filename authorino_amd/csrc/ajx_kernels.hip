@@ -14,6 +14,8 @@
 //   ajx_len_hist, ajx_len_scan, ajx_len_scatter  large batches' counting sort by length class
 //   ajx_unpermute             work-item-ordered outputs back to request order
 //   ajx_select_values<TEXT>   gjson.Get per pattern selector, from capture rows or exact
+// The per-request and per-span bodies of these kernels are in ajx_request.h and
+// ajx_stream_body.h (the host test build runs the same text).
 // Launchers: launch_eval_scan, launch_eval_stream, launch_eval_fast (the single-pass paths
 // of an EvalPlan, ajx_plan.h), launch_len_order, launch_select, launch_select_rows.
 #include <hip/hip_runtime.h>
@@ -22,103 +24,11 @@
 
 #include "ajx_fast.h"
 #include "ajx_modifiers.h"
-#include "ajx_stream.h"
+#include "ajx_stream_body.h"
 #include "ajx_kernels.h"
 #include "ajx_kcommon.h"
 
 namespace ajx {
-
-
-constexpr int kSelCache = 32;  // resolved selector values kept per request
-constexpr int kPatCache = 64;  // pattern results kept per request for the fold
-
-// MODS: the rulesets of the batch have modifier chains (ajx_modifiers.h; mb: the
-// work-item's three text buffers, the caller's scratch)
-template <bool MODS>
-__device__ __forceinline__ void eval_scan_one(uint32_t r, const uint8_t* const* __restrict__ sets,
-                                              const uint32_t* __restrict__ set_of_req,
-                                              const uint8_t* __restrict__ arena, const uint64_t* __restrict__ offs,
-                                              const uint32_t* __restrict__ lens, uint8_t* __restrict__ out_tri,
-                                              int32_t* __restrict__ out_err, uint64_t* __restrict__ out_bm,
-                                              uint32_t stride, [[maybe_unused]] ModBufs* mb) {
-    const uint8_t* blob = sets[set_of_req ? set_of_req[r] : 0];
-    const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
-    const Selector* sels = reinterpret_cast<const Selector*>(blob + h->off_selectors);
-    const Component* comps = reinterpret_cast<const Component*>(blob + h->off_components);
-    const Pattern* pats = reinterpret_cast<const Pattern*>(blob + h->off_patterns);
-    const uint32_t* code = reinterpret_cast<const uint32_t*>(blob + h->off_code);
-    const uint8_t* lits = blob + h->off_literals;
-    const uint8_t* doc = arena + offs[r];
-    const uint32_t len = lens[r];
-
-    const uint32_t ns = h->n_selectors, np = h->n_patterns;
-    ValueRef vals[kSelCache];
-    const bool cache_sel = ns <= (uint32_t)kSelCache;
-    if (cache_sel)
-        for (uint32_t s = 0; s < ns; s++)
-            vals[s] = gj_get(doc, len, comps + sels[s].comp_begin, sels[s].comp_count, lits);
-
-    auto value_of = [&](uint32_t p) -> ValueRef {
-        if (cache_sel) return vals[pats[p].selector];
-        const Selector& s = sels[pats[p].selector];
-        return gj_get(doc, len, comps + s.comp_begin, s.comp_count, lits);
-    };
-    auto eval = [&](uint32_t p) -> uint8_t {
-        const Pattern& pt = pats[p];
-        if (pt.state != P_OK) return eval_pattern<true>(blob, pt, doc, ValueRef{0, 0, T_NULL, 0});
-        if constexpr (MODS) {
-            const Selector& sl = sels[pt.selector];
-            const ValueRef v = value_of(p);
-            if (v.esc == kValList) {  // a "#." list (no modifier chain after it)
-                const uint8_t* rd;
-                ValueRef rv;
-                if (!build_list(blob, sl, doc, v, *mb, &rd, &rv)) return V_U;
-                return eval_pattern<true>(blob, pt, rd, rv);
-            }
-            if (sl.mod_count) {
-                const uint8_t* rd;
-                ValueRef rv;
-                if (!apply_modifiers(blob, sl, doc, value_of(p), *mb, &rd, &rv)) return V_U;
-                return eval_pattern<true>(blob, pt, rd, rv);
-            }
-        }
-        return eval_pattern<true>(blob, pt, doc, value_of(p));
-    };
-
-    uint8_t res[kPatCache];
-    const bool cache_pat = np <= (uint32_t)kPatCache;
-    if (out_bm) {
-        uint64_t* row = out_bm + (size_t)r * stride;
-        for (uint32_t w = 0; w < stride; w++) {
-            uint64_t word = 0;
-            for (uint32_t b = 0; b < 64; b++) {
-                uint32_t p = w * 64 + b;
-                if (p >= np) break;
-                uint8_t v = eval(p);
-                if (cache_pat) res[p] = v;
-                if (v == V_T) word |= 1ull << b;
-            }
-            row[w] = word;
-        }
-    }
-    if (cache_pat && !out_bm)
-        for (uint32_t p = 0; p < np; p++) res[p] = eval(p);
-    // one fold program per tree (a forest ruleset writes n_trees results per request)
-    const uint32_t nt = h->pad1[0] ? h->pad1[0] : 1u;
-    const uint32_t* rc = h->pad1[0] ? reinterpret_cast<const uint32_t*>(blob + h->pad1[1]) : nullptr;
-    for (uint32_t k = 0; k < nt; k++) {
-        const uint32_t* c = rc ? code + rc[2 * k] : code;
-        const uint32_t len = rc ? rc[2 * k + 1] : h->n_code;
-        int32_t ep;
-        uint8_t t;
-        if (cache_pat)
-            t = run_fold(c, len, [&](uint32_t p) { return res[p]; }, &ep);
-        else
-            t = run_fold(c, len, eval, &ep);
-        out_tri[(size_t)r * nt + k] = t;
-        if (out_err) out_err[(size_t)r * nt + k] = ep;
-    }
-}
 
 template <bool MODS>
 __global__ __launch_bounds__(256) void ajx_eval_scan(const uint8_t* const* __restrict__ sets,
@@ -222,33 +132,35 @@ __global__ __launch_bounds__(kFastMaxBlock, AJX_FAST_WAVES) void ajx_scan_fused(
     }
 }
 
-// a stage-B list entry the stream could not prove (merge_slow): the exact scan decides it
-constexpr uint32_t kStageExact = 1u << 31;
-// keep_rows bit 1 (bit 0: kKeepRows), profiling: the phase clocks of a one-request wave
-constexpr uint32_t kKeepTiming = 2u;
+// The streaming kernel (ajx_stream_body.h stream_body: the span's walk), then, with FIN (a
+// small batch without modifier chains), the stage-B list in the wave that finishes last: the
+// requests left to the exact scan and those whose stage B could not run on the LDS copy —
+// no second launch.
+//
+// The list is a call, not inlined, so that the exact scan's registers stay out of the walk's
+// own allocation (the inlined list took the kernel to 256 VGPRs, AGPR spills and ~1,400 SGPR
+// spills)
+template <bool MT>
+__device__ __noinline__ void stream_fin_list_call(const uint8_t* const* __restrict__ sets,
+                                                  const uint32_t* __restrict__ set_of_req,
+                                                  const uint8_t* __restrict__ arena, const uint64_t* __restrict__ offs,
+                                                  const uint32_t* __restrict__ lens, uint32_t cnt,
+                                                  StreamCounters* __restrict__ ctr,
+                                                  const uint32_t* __restrict__ stage_ids, uint8_t* __restrict__ out_tri,
+                                                  int32_t* __restrict__ out_err, uint64_t* __restrict__ out_bm,
+                                                  uint32_t stride, uint64_t* __restrict__ rows_out, uint32_t row_stride,
+                                                  uint32_t l) {
+    stream_fin_list<MT>(sets, set_of_req, arena, offs, lens, cnt, ctr, stage_ids, out_tri, out_err, out_bm, stride,
+                        rows_out, row_stride, l);
+}
 
-// The streaming kernel (ajx_stream.h): each wave takes a span of stream::kSpan requests in
-// arena order and reads their bytes as one coalesced stream; a lane per request then folds
-// the patterns the stream decided. Requests with a pattern left (a value to parse or
-// unescape, a regex, a long value) go with their row (found word, records, the 4 eager
-// words: row_stride >= 5 + n_rec, StreamHdr) to ajx_stream_finish through the stage-B list;
-// requests it can not prove go to the slow list (the exact scan). keep_rows (forest
-// rulesets, for authjx_select_from_eval_device): every request's row is written (slow
-// ones: kRowSlow), those with an open record through stage B. Rows: the wave-interleaved
-// layout at work-item r. Profiling: MODE 1 the structural pass only, 2 no fold.
-// Dynamic LDS: [blob copy] [per wave: WaveLds, capture rows, eager decisions].
-// MT (multi-tenant latency batches): one request per wave (per = 1) under its own
-// ruleset sets[set_of_req[r]], its tables read from global memory (L2), no blob copy.
-// LAT (small batches, no kept rows): a span that fit one step has its documents in LDS
-// still, and its lanes run stage B there (finish_full on the ring); what that leaves goes
-// to the exact scan through the stage-B list.
-template <int MODE, bool MT = false, bool LAT = false>
-__device__ __forceinline__ void stream_body(const uint8_t* const* __restrict__ sets,
+template <int MODE, bool MT = false, bool LAT = false, bool FIN = false>
+__global__ __launch_bounds__(256) void ajx_scan_stream(const uint8_t* const* __restrict__ sets,
                                                        const uint32_t* __restrict__ set_of_req,
                                                        const uint8_t* __restrict__ arena,
                                                        const uint64_t* __restrict__ offs,
                                                        const uint32_t* __restrict__ lens, uint32_t n,
-                                                       uint32_t* __restrict__ slow_count,
+                                                       StreamCounters* __restrict__ ctr,
                                                        uint32_t* __restrict__ slow_ids, uint32_t* __restrict__ stage_ids,
                                                        uint8_t* __restrict__ out_tri, int32_t* __restrict__ out_err,
                                                        uint64_t* __restrict__ out_bm, uint32_t stride, uint32_t wave_off,
@@ -258,196 +170,35 @@ __device__ __forceinline__ void stream_body(const uint8_t* const* __restrict__ s
     extern __shared__ uint4 s_stream_dyn[];
     const uint32_t w = threadIdx.x >> 6, l = threadIdx.x & 63u;
     const uint32_t span = blockIdx.x * (blockDim.x >> 6) + w;
-    // (profiling, keep_rows bit 1: lane 0 of a one-request wave writes its phases' clock
-    // counts over the request's bitmap word: blob copy | stream | stage B, 21 bits each, x16)
-    const bool timing = (keep_rows & kKeepTiming) != 0;
-    keep_rows &= kKeepRows;
-    const uint64_t c0 = timing ? __builtin_readcyclecounter() : 0ull;
-    uint64_t c1 = 0, c2 = 0;
-    const uint8_t* blob;
-    uint8_t* base;
-    if constexpr (MT) {
-        // per wave: [its ruleset's blob, when it fits wave_off bytes] [WaveLds, rows]
-        if (span >= n) return;  // (wave-uniform; per = 1)
-        const uint8_t* g = sets[set_of_req[span]];
-        uint8_t* wb = reinterpret_cast<uint8_t*>(s_stream_dyn) + w * wave_bytes;
-        const uint32_t tb = lean::uni(reinterpret_cast<const RulesetHdr*>(g)->total_bytes);  // (x16)
-        if (tb <= wave_off) {
-            copy_words_reg(reinterpret_cast<uint4*>(wb), reinterpret_cast<const uint4*>(g), tb / 16u, l, 64u);
-            wave::sync();
-            blob = wb;
-        } else {
-            blob = g;
-        }
-        base = wb + wave_off;
-    } else {
-        blob = stage_blob<true>(sets[0]);
-        base = reinterpret_cast<uint8_t*>(s_stream_dyn) + wave_off + w * wave_bytes;
-    }
-    stream::WaveLds& L = *reinterpret_cast<stream::WaveLds*>(base);
-    uint64_t* rows = reinterpret_cast<uint64_t*>(base + sizeof(stream::WaveLds));
-    if (span * per >= n) return;  // (wave-uniform)
-    if (timing) c1 = __builtin_readcyclecounter();
-    const uint64_t *rowp = nullptr, *dwp = nullptr;
-    const uint8_t* lds_doc = nullptr;
-    uint64_t* ck = L.clk;  // (timing: the step's and stage B's phase clocks)
-    if (timing) {
-        if (l < 9) ck[l] = 0;
-        wave::sync();
-    }
-    const uint32_t res = stream::scan_span<MODE>(L, rows, blob, arena, offs, lens, n, span, per, l, out_tri, out_err,
-                                                 out_bm, stride, &rowp, &dwp, LAT ? &lds_doc : nullptr,
-                                                 timing ? ck : nullptr);
-    const uint32_t r = span * per + l;
-    if (timing) c2 = __builtin_readcyclecounter();
-    auto times = [&](uint32_t rq) {
-        if (!timing || l != 0 || !out_bm) return;
-        const uint64_t c3 = __builtin_readcyclecounter();
-        auto f = [](uint64_t a, uint64_t b) { return ((b - a) >> 4) & 0x1FFFFFull; };
-        uint64_t* o = out_bm + (size_t)rq * stride;
-        o[0] = f(c0, c1) | (f(c1, c2) << 21) | (f(c2, c3) << 42);
-        if (stride >= 4 && ck[0] && ck[8]) {  // (the sub-phases: step 0..3, stage B 5..8)
-            o[1] = f(c1, ck[0]) | (f(ck[0], ck[1]) << 21) | (f(ck[1], ck[2]) << 42);
-            o[2] = f(ck[2], ck[3]) | (f(ck[3], c2) << 21) | (f(c2, ck[5]) << 42);
-            o[3] = f(ck[5], ck[6]) | (f(ck[6], ck[7]) << 21) | (f(ck[7], ck[8]) << 42);
-        }
-    };
-    if constexpr (LAT) {
-        // one request per wave: every lane takes part in its stage B (finish_full<true>)
-        if (per == 1 && wave::readlane(res == stream::R_STAGE_B && lds_doc ? 1u : 0u, 0) != 0) {
-            auto bcast = [](const void* q) {  // lane 0's pointer
-                const uint64_t v = (uint64_t)(uintptr_t)q;
-                return (uintptr_t)((uint64_t)wave::readlane((uint32_t)v, 0) |
-                                   ((uint64_t)wave::readlane((uint32_t)(v >> 32), 0) << 32));
-            };
-            const uint8_t* d0 = reinterpret_cast<const uint8_t*>(bcast(lds_doc));
-            const uint64_t* row0 = reinterpret_cast<const uint64_t*>(bcast(rowp));
-            const uint64_t* dw0 = reinterpret_cast<const uint64_t*>(bcast(dwp));
-            const uint32_t r0 = span;
-            const bool ok = stream::finish_full<true>(r0, blob, d0, lens[r0], RowRef(row0), out_tri, out_err, out_bm,
-                                                      stride, dw0, timing ? ck : nullptr);
-            if (!ok && l == 0) {
-                atomicAdd(slow_count, 1u);
-                stage_ids[atomicAdd(slow_count + 1, 1u)] = r0 | kStageExact;
-            }
-            times(r0);
-            return;
-        }
-    }
-    if (l >= per || r >= n || MODE != 0) return;
-    if constexpr (LAT) {
-        if (res == stream::R_STAGE_B && lds_doc) {
-            if (!stream::finish_full(r, blob, lds_doc, lens[r], RowRef(rowp), out_tri, out_err, out_bm, stride,
-                                     dwp)) {
-                atomicAdd(slow_count, 1u);
-                stage_ids[atomicAdd(slow_count + 1, 1u)] = r | kStageExact;
-            }
-            return;
-        }
-    }
-    const RowRef o = wave_row(rows_out, row_stride, r);
-    if (res == stream::R_SLOW) {
-        // (merge_slow: the stage-B kernel runs its exact scan, flagged on the stage-B list)
-        if (merge_slow) {
-            atomicAdd(slow_count, 1u);
-            stage_ids[atomicAdd(slow_count + 1, 1u)] = r | kStageExact;
-        } else {
-            slow_ids[atomicAdd(slow_count, 1u)] = r;
-        }
-        if (keep_rows) o[0] = kRowSlow;
-        return;
-    }
-    // (the records: the selectors', then exact selectors' prefixes')
-    const RulesetHdr* hb = reinterpret_cast<const RulesetHdr*>(blob);
-    const uint32_t ns = reinterpret_cast<const StreamHdr*>(blob + hb->off_stream)->n_rec;
-    bool open = false;
-    if (keep_rows)
-        for (uint32_t s = 0; s < ns; s++) open = open || ((rowp[1u + s] >> 32) & stream::kOpenEnd);
-    if (res == stream::R_STAGE_B || open) {
-        for (uint32_t s = 0; s <= ns; s++) o[s] = rowp[s];
-        for (uint32_t k = 0; k < 4; k++) o[1u + ns + k] = dwp[k];
-        stage_ids[atomicAdd(slow_count + 1, 1u)] = r;  // (the stage-B count follows the slow count)
-    } else if (keep_rows) {
-        for (uint32_t s = 0; s <= ns; s++) o[s] = rowp[s];
-    }
-}
-
-// The stage-B list of a small batch, run by the wave that finished last: a call, not
-// inlined, so that the exact scan's registers stay out of the walk's own allocation (the
-// inlined list took the kernel to 256 VGPRs, AGPR spills and ~1,400 SGPR spills)
-template <bool MT>
-__device__ __noinline__ void stream_fin_list(const uint8_t* const* __restrict__ sets,
-                                             const uint32_t* __restrict__ set_of_req,
-                                             const uint8_t* __restrict__ arena, const uint64_t* __restrict__ offs,
-                                             const uint32_t* __restrict__ lens, uint32_t cnt,
-                                             uint32_t* __restrict__ slow_count, const uint32_t* __restrict__ stage_ids,
-                                             uint8_t* __restrict__ out_tri, int32_t* __restrict__ out_err,
-                                             uint64_t* __restrict__ out_bm, uint32_t stride,
-                                             uint64_t* __restrict__ rows_out, uint32_t row_stride, uint32_t l) {
-    for (uint32_t i = l; i < cnt; i += 64u) {
-        const uint32_t e = stage_ids[i];
-        const uint32_t r = e & ~kStageExact;
-        const uint8_t* blob = sets[MT ? set_of_req[r] : 0];
-        bool ok = false;
-        if (!(e & kStageExact)) {
-            ok = stream::finish_full(r, blob, arena + offs[r], lens[r], wave_row(rows_out, row_stride, r), out_tri,
-                                     out_err, out_bm, stride);
-            if (!ok) atomicAdd(slow_count, 1u);
-        }
-        if (!ok)
-            eval_scan_one<false>(r, sets, MT ? set_of_req : nullptr, arena, offs, lens, out_tri, out_err, out_bm,
-                                 stride, nullptr);
-    }
-}
-
-// The kernel: the span's walk (stream_body), then, with FIN (a small batch without
-// modifier chains), the stage-B list in the wave that finishes last: the requests left to
-// the exact scan and those whose stage B could not run on the LDS copy — no second launch.
-// slow_count[2] counts the finished waves.
-template <int MODE, bool MT = false, bool LAT = false, bool FIN = false>
-__global__ __launch_bounds__(256) void ajx_scan_stream(const uint8_t* const* __restrict__ sets,
-                                                       const uint32_t* __restrict__ set_of_req,
-                                                       const uint8_t* __restrict__ arena,
-                                                       const uint64_t* __restrict__ offs,
-                                                       const uint32_t* __restrict__ lens, uint32_t n,
-                                                       uint32_t* __restrict__ slow_count,
-                                                       uint32_t* __restrict__ slow_ids, uint32_t* __restrict__ stage_ids,
-                                                       uint8_t* __restrict__ out_tri, int32_t* __restrict__ out_err,
-                                                       uint64_t* __restrict__ out_bm, uint32_t stride, uint32_t wave_off,
-                                                       uint32_t wave_bytes, uint64_t* __restrict__ rows_out,
-                                                       uint32_t row_stride, uint32_t keep_rows, uint32_t per,
-                                                       uint32_t merge_slow) {
-    stream_body<MODE, MT, LAT>(sets, set_of_req, arena, offs, lens, n, slow_count, slow_ids, stage_ids, out_tri,
-                               out_err, out_bm, stride, wave_off, wave_bytes, rows_out, row_stride, keep_rows, per,
-                               merge_slow);
+    const uint64_t c0 = (keep_rows & kKeepTiming) ? stream::clk_now() : 0ull;  // (profiling)
+    const uint8_t* blob0 = MT ? nullptr : stage_blob<true>(sets[0]);
+    stream_body<MODE, MT, LAT>(sets, set_of_req, arena, offs, lens, n, ctr, slow_ids, stage_ids, out_tri, out_err,
+                               out_bm, stride, wave_off, wave_bytes, rows_out, row_stride, keep_rows, per, merge_slow,
+                               reinterpret_cast<uint8_t*>(s_stream_dyn), w, l, span, blob0, c0);
     if constexpr (FIN) {
-        const uint32_t l = threadIdx.x & 63u;
         __threadfence();  // (this wave's stage-B list entries and rows, before its count)
         uint32_t last = 0;
-        if (l == 0) last = atomicAdd(slow_count + 2, 1u) + 1u == gridDim.x * (blockDim.x >> 6) ? 1u : 0u;
+        if (l == 0) last = atomicAdd(&ctr->waves_done, 1u) + 1u == gridDim.x * (blockDim.x >> 6) ? 1u : 0u;
         if (!wave::readlane(last, 0)) return;
         __threadfence();
-        const uint32_t cnt = __hip_atomic_load(slow_count + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t cnt = __hip_atomic_load(&ctr->stage_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (cnt)
-            stream_fin_list<MT>(sets, set_of_req, arena, offs, lens, cnt, slow_count, stage_ids, out_tri, out_err,
-                                out_bm, stride, rows_out, row_stride, l);
+            stream_fin_list_call<MT>(sets, set_of_req, arena, offs, lens, cnt, ctr, stage_ids, out_tri, out_err, out_bm,
+                                     stride, rows_out, row_stride, l);
         // every other wave is done with the counters: back to zero for the next launch on
-        // this stream (no fill before it), the slow count kept at [3] for the host
+        // this stream (no fill before it), the slow count published for the host
         __threadfence();
         if (l == 0) {
-            slow_count[3] = __hip_atomic_load(slow_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            slow_count[0] = 0;
-            slow_count[1] = 0;
-            slow_count[2] = 0;
+            ctr->exact_published = __hip_atomic_load(&ctr->slow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ctr->slow = 0;
+            ctr->stage_b = 0;
+            ctr->waves_done = 0;
         }
     }
 }
 
-// Stage B of the streaming kernel: one work-item per request on the stage-B list, on its
-// row in HBM (stream::finish_full); what it can not decide goes to the slow list. MT: each
-// request's own ruleset, read from global memory. EXACT (small batches, one launch fewer):
-// the exact scan runs here, for the requests the stream flagged (kStageExact) and for those
-// stage B can not decide; 1 without, 2 with modifier buffers.
+// Stage B of the streaming kernel: one work-item per request on the stage-B list
+// (stream_finish_entry). MT, EXACT: there.
 template <bool MT = false, int EXACT = 0>
 __global__ __launch_bounds__(256) void ajx_stream_finish(const uint8_t* const* __restrict__ sets,
                                                          const uint32_t* __restrict__ set_of_req,
@@ -456,32 +207,27 @@ __global__ __launch_bounds__(256) void ajx_stream_finish(const uint8_t* const* _
                                                          const uint32_t* __restrict__ lens,
                                                          const uint32_t* __restrict__ stage_ids,
                                                          uint64_t* __restrict__ rows, uint32_t row_stride,
-                                                         uint32_t* __restrict__ slow_count,
+                                                         StreamCounters* __restrict__ ctr,
                                                          uint32_t* __restrict__ slow_ids, uint8_t* __restrict__ out_tri,
                                                          int32_t* __restrict__ out_err, uint64_t* __restrict__ out_bm,
                                                          uint32_t stride) {
     const uint8_t* blob0 = MT ? nullptr : stage_blob<true>(sets[0]);
-    const uint32_t cnt = slow_count[1];  // (the stage-B count)
+    const uint32_t cnt = ctr->stage_b;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += gridDim.x * blockDim.x) {
-        const uint32_t e = stage_ids[i];
-        const uint32_t r = e & ~kStageExact;
-        const uint8_t* blob = MT ? sets[set_of_req[r]] : blob0;
-        bool ok = false;
-        if (!(e & kStageExact))
-            ok = stream::finish_full(r, blob, arena + offs[r], lens[r], wave_row(rows, row_stride, r), out_tri,
-                                     out_err, out_bm, stride);
-        if (ok) continue;
-        if constexpr (EXACT == 0) {
-            slow_ids[atomicAdd(slow_count, 1u)] = r;
+        if constexpr (!MT && EXACT == 0) {
+            // (this instance keeps the entry in its own words: calling stream_finish_entry<false, 0>,
+            // which the host tests run, it named one vector register more)
+            const uint32_t e = stage_ids[i];
+            const uint32_t r = e & ~kStageExact;
+            bool ok = false;
+            if (!(e & kStageExact))
+                ok = stream::finish_full(r, blob0, arena + offs[r], lens[r], wave_row(rows, row_stride, r), out_tri,
+                                         out_err, out_bm, stride);
+            if (ok) continue;
+            slow_ids[atomicAdd(&ctr->slow, 1u)] = r;
         } else {
-            if (!(e & kStageExact)) atomicAdd(slow_count, 1u);
-            if constexpr (EXACT == 2) {
-                ModBufs mb;
-                eval_scan_one<true>(r, sets, set_of_req, arena, offs, lens, out_tri, out_err, out_bm, stride, &mb);
-            } else {
-                eval_scan_one<false>(r, sets, set_of_req, arena, offs, lens, out_tri, out_err, out_bm, stride,
-                                     nullptr);
-            }
+            stream_finish_entry<MT, EXACT>(stage_ids[i], blob0, sets, set_of_req, arena, offs, lens, rows, row_stride,
+                                           ctr, slow_ids, out_tri, out_err, out_bm, stride);
         }
     }
 }
@@ -544,10 +290,12 @@ hipError_t launch_eval_stream(const Batch& b, const Results& res, const Work& wo
     const bool merge = mt || per < stream::kSpan;
     const uint32_t spans = (n + per - 1) / per;
     const uint32_t grid = (spans + block / 64 - 1) / (block / 64);
-    // (one fill: the slow count, the stage-B count and the finished-wave count after it;
-    // none after a FIN launch on this stream, whose last wave cleared them)
+    // (one fill: the slow count, the stage-B count and the finished-wave count; none after a
+    // FIN launch on this stream, whose last wave cleared them)
+    StreamCounters* const ctr = stream_counters(work.slow_count);
     hipError_t e = hipSuccess;
-    if (!was_zero && (e = hipMemsetAsync(work.slow_count, 0, 3 * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    if (!was_zero && (e = hipMemsetAsync(ctr, 0, offsetof(StreamCounters, exact_published), stream)) != hipSuccess)
+        return e;
     static std::atomic<uint64_t> attr_done{0};
     e = attr_once(attr_done, [] {
         for (const void* k : {reinterpret_cast<const void*>(&ajx_scan_stream<0>),
@@ -577,8 +325,8 @@ hipError_t launch_eval_stream(const Batch& b, const Results& res, const Work& wo
     if (e != hipSuccess) return e;
 #define AJX_STREAM_LAUNCH(M, T, LT, F)                                                                           \
     hipLaunchKernelGGL((ajx_scan_stream<M, T, LT, F>), dim3(grid), dim3(block), lds, stream, b.sets, b.set_of_req, \
-                       b.arena, b.offs, b.lens, n, work.slow_count, work.slow_ids, d_stage_ids, res.tri, res.err,  \
-                       res.bm, res.stride, wave_off, wave_bytes, work.rows, work.row_stride,                        \
+                       b.arena, b.offs, b.lens, n, ctr, work.slow_ids, d_stage_ids, res.tri, res.err, res.bm,      \
+                       res.stride, wave_off, wave_bytes, work.rows, work.row_stride,                                \
                        (keep_rows ? kKeepRows : 0u) | (timing ? kKeepTiming : 0u), per, merge ? 1u : 0u)
     const bool lat = merge && !keep_rows;
     // (stage B and the exact scan in the last wave: no second launch). Only for batches of at
@@ -612,7 +360,7 @@ hipError_t launch_eval_stream(const Batch& b, const Results& res, const Work& wo
 #define AJX_FINISH_LAUNCH(T, X, LDS)                                                                            \
     hipLaunchKernelGGL((ajx_stream_finish<T, X>), dim3(fgrid), dim3(256), LDS, stream, b.sets,                     \
                        T ? b.set_of_req : nullptr, b.arena, b.offs, b.lens, d_stage_ids, work.rows,                \
-                       work.row_stride, work.slow_count, work.slow_ids, res.tri, res.err, res.bm, res.stride)
+                       work.row_stride, ctr, work.slow_ids, res.tri, res.err, res.bm, res.stride)
     if (mt && mods)
         AJX_FINISH_LAUNCH(true, 2, 0);
     else if (mt)
@@ -756,12 +504,7 @@ hipError_t launch_len_order(const uint32_t* d_lens, uint32_t n, uint32_t* d_hist
 }
 
 // gjson.Get per pattern selector (the response / header selectors of SURVEY.md §8 a14):
-// one work-item per request, the exact device Get (gj_get) for each of the ruleset's
-// patterns; out[r * stride + p] = {start (relative to the document), len, type, esc}.
-// An UNSUPPORTED selector reports type 0xFF. TEXT: a selector with modifiers and a "#."
-// list resolve to built text, copied into the request's slot text[r * text_stride ...]
-// (select_value, ajx_modifiers.h; 0xFF when it does not fit); without TEXT they report
-// 0xFF (the capture-row path of select_from_eval).
+// one work-item per request (select_request, ajx_request.h).
 template <bool TEXT>
 __global__ __launch_bounds__(256) void ajx_select_values(const uint8_t* const* __restrict__ sets,
                                                          const uint32_t* __restrict__ set_of_req,
@@ -778,69 +521,8 @@ __global__ __launch_bounds__(256) void ajx_select_values(const uint8_t* const* _
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const uint32_t r = perm ? perm[k] : k;
-    // the single-pass scan's capture row when it has one (not on the slow list)
-    const RowRef row = !rows ? RowRef() : wave_rows ? wave_row(const_cast<uint64_t*>(rows), row_stride, k)
-                                                    : RowRef(rows + (size_t)r * row_stride);
-    const uint64_t found = rows ? row[0] : kRowSlow;
-    const uint8_t* blob = sets[set_of_req ? set_of_req[r] : 0];
-    const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
-    const Selector* sels = reinterpret_cast<const Selector*>(blob + h->off_selectors);
-    const Component* comps = reinterpret_cast<const Component*>(blob + h->off_components);
-    const Pattern* pats = reinterpret_cast<const Pattern*>(blob + h->off_patterns);
-    const uint8_t* lits = blob + h->off_literals;
-    const uint8_t* doc = arena + offs[r];
-    const uint32_t len = lens[r];
-    // patterns [p0, p0 + stride): the whole ruleset (p0 = 0) or, after a forest
-    // evaluation, the response selectors compiled as its last tree
-    const uint32_t avail = h->n_patterns > p0 ? h->n_patterns - p0 : 0u;
-    const uint32_t np = avail < stride ? avail : stride;
-    [[maybe_unused]] uint32_t used = 0;  // (TEXT: bytes of the request's text slot taken)
-    for (uint32_t q = 0; q < np; q++) {
-        const uint32_t p = p0 + q;
-        uint32_t* o = out + ((size_t)r * stride + q) * 3;
-        const uint32_t si = pats[p].selector;
-        if (pats[p].state == P_UNSUPPORTED || (!TEXT && sels[si].mod_count)) {
-            o[0] = 0;
-            o[1] = 0;
-            o[2] = 0xFFu;
-            continue;
-        }
-        if constexpr (TEXT) {
-            if (sels[si].mod_count) {
-                ModBufs mb;
-                if (!select_value(blob, sels[si], doc, len, mb, text + (size_t)r * text_stride, text_stride, &used, o))
-                    o[0] = 0, o[1] = 0, o[2] = 0xFFu;
-                continue;
-            }
-        }
-        if (!(found & kRowSlow)) {
-            if ((found >> si) & 1u) {
-                const uint64_t rec = row[1 + si];
-                const uint32_t meta = (uint32_t)(rec >> 32);
-                o[0] = (uint32_t)rec;
-                o[1] = meta & 0xFFFFFFu;
-                o[2] = ((meta >> 24) & 7u) | (((meta >> 27) & 1u) << 8);
-            } else {
-                o[0] = 0;
-                o[1] = 0;
-                o[2] = T_NULL;
-            }
-            continue;
-        }
-        const Selector& sl = sels[si];
-        const ValueRef v = gj_get(doc, len, comps + sl.comp_begin, sl.comp_count, lits);
-        o[0] = v.start;
-        o[1] = v.end - v.start;
-        o[2] = (uint32_t)v.type | ((uint32_t)v.esc << 8);
-        if (v.esc == kValList) {  // a "#." list: built text (without TEXT: not selectable)
-            o[2] = 0xFFu;
-            if constexpr (TEXT) {
-                ModBufs mb;
-                if (!select_value(blob, sl, doc, len, mb, text + (size_t)r * text_stride, text_stride, &used, o))
-                    o[0] = 0, o[1] = 0, o[2] = 0xFFu;
-            }
-        }
-    }
+    select_request<TEXT>(r, k, sets, set_of_req, arena, offs, lens, out, stride, rows, row_stride, p0, wave_rows, text,
+                         text_stride);
 }
 
 hipError_t launch_select(const Batch& b, uint32_t shared_blob_bytes, const Values& v, const Work& work,

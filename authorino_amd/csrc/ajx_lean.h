@@ -37,6 +37,7 @@
 // Output: the request's capture row (ajx_stageb.h's format, for its stage B).
 #pragma once
 #include "ajx_lean_cls.h"
+#include "ajx_wave.h"
 
 namespace ajx {
 namespace lean {
@@ -883,4 +884,39 @@ struct CopyLoader {
 };
 
 }  // namespace lean
+
+// What the lean kernels do to request r (ajx_scan_lean, and the tenant kernel's wave of one
+// ruleset): eligible, the lean scan through ld (the kernels' DmaLoader, the host tests'
+// CopyLoader) into row, stage B with its outputs at index o, and the slow mark: a request that
+// any step hands to the exact scan ends with row[0] = kRowSlow (scan_doc's failure path
+// marks the row itself) and one entry on the slow list. lane_ring: the lane's 16 bytes of
+// every ring chunk; span_buf: its kSpanStride bytes for stage B's value copies (the ring
+// again: scan_doc leaves no load in flight). It lives here, not in ajx_request.h, which
+// ajx_kernels.hip compiles without the walker.
+// ABL, ARR: lean::scan_doc's (an ablation ends after the scan).
+template <int ABL, bool ARR, class Loader>
+AJX_HD void lean_request(uint32_t r, uint32_t o, const uint8_t* blob, const uint8_t* d, uint32_t len, RowRef row,
+                         uint8_t* lane_ring, uint8_t* span_buf, Loader ld, uint32_t keep_rows, uint32_t* slow_count,
+                         uint32_t* slow_ids, uint8_t* out_tri, int32_t* out_err, uint64_t* out_bm, uint32_t stride,
+                         uint64_t dec[2]) {
+    bool ok = lean::eligible(reinterpret_cast<const RulesetHdr*>(blob), len);
+    if (ok) {
+        ok = lean::scan_doc<ABL, ARR>(blob, len, (uint32_t)((uintptr_t)d & 15u), row, lane_ring, ld, dec, keep_rows);
+    } else {
+        row[0] = kRowSlow;
+    }
+    if constexpr (ABL != 0) {
+        if (dec[0] ^ dec[1]) row[0] ^= dec[0] ^ dec[1];
+        return;
+    }
+    if (!ok) {
+        slow_ids[wave::global_add(slow_count, 1u)] = r;
+        return;
+    }
+    if (!finish_request(o, blob, d, row, out_tri, out_err, out_bm, stride, dec, span_buf)) {
+        row[0] = kRowSlow;
+        slow_ids[wave::global_add(slow_count, 1u)] = r;
+    }
+}
+
 }  // namespace ajx

@@ -45,31 +45,12 @@ __global__ __launch_bounds__(AJX_LEAN_MAXBLOCK, AJX_LEAN_WAVES) void ajx_scan_le
     uint8_t* wring = reinterpret_cast<uint8_t*>(s_lean_dyn) + ring_off + (threadIdx.x >> 6) * lean::kRingBytesPerWave;
     const RowRef row = wave_row(rows, row_stride, k);
     const uint8_t* d = arena + offs[r];
-    const uint32_t len = lens[r];
-    const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
-    bool ok = lean::eligible(h, len);
+    const uint32_t len = lens[r], lane = threadIdx.x & 63u;
+    const uint32_t mis = (uint32_t)((uintptr_t)d & 15u);
     uint64_t dec[2] = {0ull, 0ull};
-    if (ok) {
-        const uint32_t mis = (uint32_t)((uintptr_t)d & 15u);
-        lean::DmaLoader ld{reinterpret_cast<const uint4*>(d - mis), (len + mis + 15u) / 16u, wring};
-        ok = lean::scan_doc<ABL, ARR>(blob, len, mis, row, wring + (threadIdx.x & 63u) * 16u, ld, dec, keep_rows);
-    } else {
-        row[0] = kRowSlow;
-    }
-    if constexpr (ABL != 0) {
-        if (dec[0] ^ dec[1]) row[0] ^= dec[0] ^ dec[1];
-        return;
-    }
-    if (!ok) {
-        slow_ids[atomicAdd(slow_count, 1u)] = r;
-        return;
-    }
-    // (stage B reads short values from a copy in the lane's share of the ring, stage_span:
-    // scan_doc left no load in flight)
-    if (!finish_request(o, blob, d, row, out_tri, out_err, out_bm, stride, dec, wring + (threadIdx.x & 63u) * kSpanStride)) {
-        row[0] = kRowSlow;
-        slow_ids[atomicAdd(slow_count, 1u)] = r;
-    }
+    lean_request<ABL, ARR>(r, o, blob, d, len, row, wring + lane * 16u, wring + lane * kSpanStride,
+                           lean::DmaLoader{reinterpret_cast<const uint4*>(d - mis), (len + mis + 15u) / 16u, wring},
+                           keep_rows, slow_count, slow_ids, out_tri, out_err, out_bm, stride, dec);
 }
 
 #define AJX_LEAN_K(SH, A, F) reinterpret_cast<const void*>(&ajx_scan_lean<SH, A, F>)
@@ -193,8 +174,8 @@ __global__ __launch_bounds__(kFastBlock, AJX_FAST_WAVES) void ajx_scan_fused_ten
     // (wave-uniform: the whole wave takes the LDS tables or the global ones)
     if (__all(ridx < nst)) {
         // a wave whose requests all use one staged ruleset (the caller's bucketing makes most
-        // waves so: 84 % of c4's) runs the lean scan on that copy (ajx_scan_lean's
-        // per-request body); a wave of several rulesets, the token scanner with each lane's
+        // waves so: 84 % of c4's) runs the lean scan on that copy (lean_request,
+        // as ajx_scan_lean); a wave of several rulesets, the token scanner with each lane's
         // own copy. (As two kernels, one per kind of wave, each with its own registers: c4
         // 5.57 ms against 4.85 ms for this one.)
         const uint32_t off0 = lean::uni(my_off);
@@ -202,20 +183,12 @@ __global__ __launch_bounds__(kFastBlock, AJX_FAST_WAVES) void ajx_scan_fused_ten
             const uint8_t* blob = reinterpret_cast<const uint8_t*>(s_stage) + off0;
             if (k >= n) return;
             const uint32_t len = lens[r];
-            const RulesetHdr* h = reinterpret_cast<const RulesetHdr*>(blob);
+            uint8_t* wring = reinterpret_cast<uint8_t*>(s_stage) + ring_off + wv * lean::kRingBytesPerWave;
+            const uint32_t mis = (uint32_t)((uintptr_t)d & 15u);
             uint64_t dec[2] = {0ull, 0ull};
-            bool ok = lean::eligible(h, len);
-            if (ok) {
-                uint8_t* wring = reinterpret_cast<uint8_t*>(s_stage) + ring_off + wv * lean::kRingBytesPerWave;
-                const uint32_t mis = (uint32_t)((uintptr_t)d & 15u);
-                lean::DmaLoader ld{reinterpret_cast<const uint4*>(d - mis), (len + mis + 15u) / 16u, wring};
-                ok = lean::scan_doc(blob, len, mis, row, wring + lane * 16u, ld, dec, 0u) &&
-                     finish_request(r, blob, d, row, out_tri, out_err, out_bm, stride, dec, wring + lane * kSpanStride);
-            }
-            if (!ok) {
-                row[0] = kRowSlow;
-                slow_ids[atomicAdd(slow_count, 1u)] = r;
-            }
+            lean_request<0, true>(r, r, blob, d, len, row, wring + lane * 16u, wring + lane * kSpanStride,
+                                  lean::DmaLoader{reinterpret_cast<const uint4*>(d - mis), (len + mis + 15u) / 16u, wring},
+                                  0u, slow_count, slow_ids, out_tri, out_err, out_bm, stride, dec);
             return;
         }
     }

@@ -15,6 +15,33 @@ constexpr uint32_t kMaxSharedBlobBytes = 48 * 1024;
 constexpr uint32_t kMaxTenantStageBytes = 16 * 1024;
 constexpr uint32_t kStreamSpan = 32;  // requests per wave at most (stream::kSpan)
 
+// The streaming path's counters, the first words of a workspace's slow buffer; its slow ids
+// follow them (stream_slow_ids). One fill zeroes the first three before a launch. (The other
+// paths keep one u32 count there and their ids from word 1.)
+struct StreamCounters {
+    uint32_t slow;        // requests the exact scan decides (the slow list's length)
+    uint32_t stage_b;     // entries on the stage-B list
+    uint32_t waves_done;  // waves that finished their span (the small-batch instance elects the last)
+    uint32_t exact_published;  // the slow count for the host, kept by the wave that zeroed the others
+};
+constexpr uint32_t kStreamCounterWords = sizeof(StreamCounters) / sizeof(uint32_t);
+inline StreamCounters* stream_counters(uint32_t* slow_buf) { return reinterpret_cast<StreamCounters*>(slow_buf); }
+inline uint32_t* stream_slow_ids(uint32_t* slow_buf) { return slow_buf + kStreamCounterWords; }
+
+// A workspace's order buffer for n requests: perm[n] | histogram, kPermHistWords | pos_of[n]
+// (launch_len_order). The streaming path, which takes no length order, uses the whole
+// buffer as its stage-B list (n entries at most).
+constexpr uint32_t kPermHistWords = 4096;  // (the sort needs 2 x 1024 + 1)
+struct PermBuf {
+    uint32_t* p;
+    uint32_t n;
+    static constexpr uint64_t words(uint32_t n) { return 2ull * n + kPermHistWords; }
+    uint32_t* perm() const { return p; }
+    uint32_t* hist() const { return p + n; }
+    uint32_t* pos_of() const { return p + n + kPermHistWords; }
+    uint32_t* stage_list() const { return p; }
+};
+
 // Kernel modes (authjx_debug_ablate; bench.py --kernel-mode). 0 is the product; the others
 // are for profiling and comparison. The numbers are what the scripts and DESIGN use.
 enum KernelMode : int {

@@ -106,6 +106,8 @@ AJX_HD T readlane_t(const T& x, uint32_t l) {
 AJX_HD void lds_min(uint32_t* p, uint32_t v) { atomicMin(p, v); }
 AJX_HD void lds_or64(uint64_t* p, uint64_t v) { atomicOr((unsigned long long*)p, (unsigned long long)v); }
 AJX_HD uint32_t lds_cas(uint32_t* p, uint32_t cmp, uint32_t v) { return atomicCAS(p, cmp, v); }
+// global atomics (the kernels' counters and list cursors): the value before the add
+AJX_HD uint32_t global_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
 
 #else  // host emulation (tests only): 64 threads per wave
 
@@ -220,6 +222,7 @@ inline uint32_t lds_cas(uint32_t* p, uint32_t cmp, uint32_t v) {
     __atomic_compare_exchange_n(p, &cmp, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
     return cmp;
 }
+inline uint32_t global_add(uint32_t* p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 
 // runs body(lane) on 64 threads as one emulated wave
 template <class Body>

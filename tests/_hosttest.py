@@ -244,6 +244,15 @@ def lean_keep(keep: bool) -> None:
     L.ht_lean_keep(1 if keep else 0)
 
 
+def lean_arr(arr: bool) -> None:
+    """arr True: eval_lean runs the array-walking instance of lean_request for every ruleset
+    (ajx_scan_lean without a staged blob, the tenant kernel); False: the launcher's choice
+    by the ruleset's kLeanArr."""
+    L = lib()
+    L.ht_lean_arr.argtypes = [C.c_int]
+    L.ht_lean_arr(1 if arr else 0)
+
+
 def eval_lean(hr: "HostRuleset", doc, mis: int = 0, n_sel: int = 0):
     """The lean single-pass scan (ajx_lean.h) + stage B on the host: (tri | -1 exact scan |
     -2 not eligible, err, res, capture row or None)."""
@@ -278,15 +287,39 @@ def json_valid(text) -> int:
     return lib().ht_json_valid(d, len(d))
 
 
-def eval_stream(hr, arena, offs, lens, mode=0, stride=2, dbg=None, per=0):
-    """The streaming scan (ajx_stream.h) over a batch on the host emulation of the wave,
-    then its stage B: (tri, err, bitmap, slow) — slow[r] = 1 where request r goes to the
-    exact scan, 2 where stage B decided it; None when the ruleset has no stream tables.
-    per: requests per wave (0: 32)."""
+def eval_exact(hr, doc, mods=-1, stride=0, n_trees=1):
+    """eval_scan_one (the exact scan's body) for one document: (tri per tree, err per tree,
+    bitmap words or None). mods: the instance (-1: as the launcher picks it); stride: words
+    of the bitmap row, poisoned before the call (0: no bitmap)."""
+    L = lib()
+    L.ht_eval_exact.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
+                                C.c_void_p]
+    L.ht_eval_exact.restype = None
+    d = _b(doc)
+    tri = (C.c_uint8 * n_trees)(*([0xEE] * n_trees))
+    err = (C.c_int32 * n_trees)(*([-7] * n_trees))
+    bm = (C.c_uint64 * max(stride, 1))(*([0xFFFFFFFFFFFFFFFF] * max(stride, 1)))
+    L.ht_eval_exact(hr._h, d, len(d), mods, stride, tri, err, bm)
+    return list(tri), list(err), (list(bm)[:stride] if stride else None)
+
+
+def eval_stream(hr, arena, offs, lens, mode=0, stride=2, dbg=None, per=0, hr2=None, set_of_req=None, wave_off=0,
+                keep_rows=False, merge_slow=None, fin=False, rows=None, row_stride=0, lists=False, n_out=1):
+    """The streaming kernels' bodies (ajx_stream_body.h) over a batch on the host emulation
+    of the wave, as launch_eval_stream runs them: the spans, the stage-B list (fin: by
+    stream_fin_list, else by stream_finish_entry), the exact scan of the slow list:
+    (tri, err, bitmap, slow) — slow[r] = 1 where the exact scan decided request r, 2 where
+    stage B did; None when a ruleset has no stream tables. per: requests per wave (0: 32).
+    hr2, set_of_req, wave_off: the multi-tenant instance (request r under hr2 where
+    set_of_req[r], wave_off bytes of room for a wave's own blob copy). keep_rows, rows
+    (np.uint64, the wave layout, row_stride words per row): every request's row kept.
+    merge_slow: None as the launcher. lists: also return a dict of the lists' state."""
     L = lib()
     if not getattr(L, "_stream_decl", False):
-        L.ht_eval_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
-                                     C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32]
+        L.ht_eval_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint32,
+                                     C.c_void_p]
         L.ht_eval_stream.restype = C.c_int
         L._stream_decl = True
     import numpy as np
@@ -295,16 +328,53 @@ def eval_stream(hr, arena, offs, lens, mode=0, stride=2, dbg=None, per=0):
     a = np.concatenate([np.asarray(arena, dtype=np.uint8), np.zeros(64, np.uint8)])
     offs = np.ascontiguousarray(offs, dtype=np.uint64)
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
-    tri = np.full(n, 0xEE, np.uint8)
-    err = np.full(n, -7, np.int32)
+    tri = np.full(n * n_out, 0xEE, np.uint8)
+    err = np.full(n * n_out, -7, np.int32)
     bm = np.zeros((n, stride), np.uint64)
     slow = np.zeros(n, np.uint8)
-    rc = L.ht_eval_stream(hr._h, a.ctypes.data, offs.ctypes.data, lens.ctypes.data, n, tri.ctypes.data,
+    sor = None if set_of_req is None else np.ascontiguousarray(set_of_req, dtype=np.uint32)
+    lst = np.zeros(4 + 2 * n, np.uint32)
+    rc = L.ht_eval_stream(hr._h, None if hr2 is None else hr2._h, None if sor is None else sor.ctypes.data, wave_off,
+                          a.ctypes.data, offs.ctypes.data, lens.ctypes.data, n, tri.ctypes.data,
                           err.ctypes.data, bm.ctypes.data, stride, slow.ctypes.data, mode,
-                          None if dbg is None else dbg.ctypes.data, per)
+                          None if dbg is None else dbg.ctypes.data, per, 1 if keep_rows else 0,
+                          -1 if merge_slow is None else int(bool(merge_slow)), 1 if fin else 0,
+                          None if rows is None else rows.ctypes.data, row_stride, lst.ctypes.data)
+    assert rc != -3, "a combination launch_eval_stream never makes"
     if rc < 0:
         return None
+    if n_out > 1:
+        tri, err = tri.reshape(n, n_out), err.reshape(n, n_out)
+    if lists:
+        return tri, err, bm, slow, {"slow_after_spans": int(lst[0]), "stage": [int(x) for x in lst[4:4 + lst[1]]],
+                                    "slow_final": int(lst[2]), "slow_ids": [int(x) for x in lst[4 + n:4 + n + lst[3]]]}
     return tri, err, bm, slow
+
+
+STAGE_EXACT = 1 << 31  # ajx::kStageExact: a stage-B list entry the exact scan decides
+ROW_SLOW = 1 << 63     # ajx::kRowSlow
+
+
+def select_rows(hr, arena, offs, lens, stride, rows=None, row_stride=0, p0=0, wave_rows=False, text_stride=0):
+    """select_request (the select kernel's body) per request: out[n][stride][3] = {start, len,
+    type | esc << 8}, from capture rows (np.uint64) or, without, the exact Get. text_stride:
+    the TEXT instance with that many bytes per request (returns (out, text))."""
+    import numpy as np
+
+    L = lib()
+    L.ht_select_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                 C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.ht_select_rows.restype = None
+    n = len(lens)
+    a = np.concatenate([np.asarray(arena, dtype=np.uint8), np.zeros(64, np.uint8)])
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    out = np.full((n, stride, 3), 0xABABABAB, np.uint32)
+    text = np.zeros(max(n * text_stride, 1), np.uint8)
+    L.ht_select_rows(hr._h, a.ctypes.data, offs.ctypes.data, lens.ctypes.data, n, out.ctypes.data, stride,
+                     None if rows is None else rows.ctypes.data, row_stride, p0, 1 if wave_rows else 0,
+                     text.ctypes.data if text_stride else None, text_stride)
+    return (out, text) if text_stride else out
 
 
 class PlanIn(C.Structure):

@@ -124,12 +124,12 @@ bool stream_eligible(const uint8_t*, uint32_t) { return true; }
 uint32_t stream_records(const uint8_t*) { return 1; }
 hipError_t launch_eval_stream(const Batch& b, const Results& res, const Work& work, const EvalPlan& plan, uint32_t,
                               uint32_t, uint32_t*, bool* zero, hipStream_t) {
-    // (as the small-batch instance: the counters left zero, the slow count at [3])
-    work.slow_count[3] = b.n / 5;
-    work.slow_count[0] = work.slow_count[1] = work.slow_count[2] = 0;
+    // (as the small-batch instance: the counters left zero, the slow count published)
+    StreamCounters* ctr = stream_counters(work.slow_count);
+    *ctr = StreamCounters{0, 0, 0, b.n / 5};
     if (zero) *zero = !plan.keep_rows;
     if (plan.keep_rows) {
-        work.slow_count[0] = b.n / 5;
+        ctr->slow = b.n / 5;
         for (uint32_t r = 0; r < b.n; r++) work.rows[(size_t)r * work.row_stride] = r;
     }
     results(b.n, res.tri, res.err, res.bm, res.stride);

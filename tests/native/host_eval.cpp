@@ -2,23 +2,62 @@
 // (authorino_amd/csrc/ajx_device.h) and the reconcile-time compiler for the host CPU so
 // the CPU test suite can check them against the oracle without a GPU. It is not part
 // of libauthjx.so and is never used by the product path (which has no CPU fallback).
+// What the kernels do to one request or one span it calls as the kernels do, from
+// ajx_request.h, ajx_lean.h (lean_request) and ajx_stream_body.h: it holds no copy of those
+// bodies.
 #define AJX_HD inline
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../authorino_amd/csrc/ajx_compiler.h"
-#include "../../authorino_amd/csrc/ajx_fast.h"
 #define AJX_LEAN_COUNT 1
 #include "../../authorino_amd/csrc/ajx_lean.h"
-#include "../../authorino_amd/csrc/ajx_modifiers.h"
+#include "../../authorino_amd/csrc/ajx_request.h"
 #include "../../authorino_amd/csrc/ajx_regex.h"
 
 using namespace ajx;
 
 struct HtRuleset {
     CompiledRuleset c;
+    // the same patterns as a forest of one-pattern trees: the exact scan of it writes every
+    // pattern's tri-state as a tree's result (ht_eval's res[]). Empty when it did not compile
+    // or is not one tree per pattern of c: ht_eval then reads res[] as stage_b() reads a
+    // bitmap (T bit, static E, unsupported, else F), which hides runtime U and E
+    CompiledRuleset probe;
 };
+
+// (pats: the ruleset's patterns in order)
+static void build_probe(HtRuleset* r, const std::vector<authjx_pattern>& pats) {
+    std::vector<authjx_node> leaf(pats.size());
+    std::vector<authjx_tree> trees(pats.size());
+    for (size_t p = 0; p < pats.size(); p++) {
+        leaf[p] = authjx_node{AUTHJX_NODE_PATTERN, -1, -1, 0};
+        trees[p] = authjx_tree{&pats[p], 1, &leaf[p], 1, 0};
+    }
+    std::string e;
+    if (pats.empty() || compile_forest(trees.data(), (uint32_t)trees.size(), &r->probe, &e) != AUTHJX_OK ||
+        r->probe.n_patterns != r->c.n_patterns ||
+        ((const RulesetHdr*)r->probe.blob.data())->pad1[0] != r->c.n_patterns)  // (one result per pattern)
+        r->probe = CompiledRuleset();
+}
+
+// the exact scan's body (eval_scan_one, the instance the launcher takes for the ruleset) for
+// one document: tri / err per tree, bm (or null) of `stride` words
+static void exact_one(const uint8_t* blob, const uint8_t* doc, uint32_t len, int mods, uint8_t* tri, int32_t* err,
+                      uint64_t* bm, uint32_t stride) {
+    const RulesetHdr* hd = (const RulesetHdr*)blob;
+    const uint8_t* sets[1] = {blob};
+    const uint64_t offs[1] = {0};
+    const uint32_t lens[1] = {len};
+    if (mods < 0) mods = hd->n_modifiers != 0 || (hd->flags & kFlagBufs) != 0;
+    if (mods) {
+        static thread_local ModBufs mb;  // (the kernel's work-item scratch)
+        eval_scan_one<true>(0, sets, nullptr, doc, offs, lens, tri, err, bm, stride, &mb);
+    } else {
+        eval_scan_one<false>(0, sets, nullptr, doc, offs, lens, tri, err, bm, stride, nullptr);
+    }
+}
 
 extern "C" {
 
@@ -30,6 +69,7 @@ void* ht_compile(const authjx_tree* tree, int32_t* status, char* err, size_t cap
     if (*rc != AUTHJX_OK) { delete r; return nullptr; }
     if (status)
         for (uint32_t i = 0; i < r->c.n_patterns; i++) status[i] = r->c.pattern_status[i];
+    build_probe(r, std::vector<authjx_pattern>(tree->patterns, tree->patterns + tree->n_patterns));
     return r;
 }
 
@@ -40,51 +80,61 @@ void* ht_compile_forest(const authjx_tree* trees, uint32_t n, char* err, size_t 
     *rc = compile_forest(trees, n, &r->c, &e);
     if (err && cap) std::snprintf(err, cap, "%s", e.c_str());
     if (*rc != AUTHJX_OK) { delete r; return nullptr; }
+    std::vector<authjx_pattern> pats;
+    for (uint32_t k = 0; k < n; k++) pats.insert(pats.end(), trees[k].patterns, trees[k].patterns + trees[k].n_patterns);
+    build_probe(r, pats);
     return r;
 }
 
 void ht_free(void* h) { delete (HtRuleset*)h; }
 
-// evaluate one document; res[p] receives each pattern's tri-state
+// The exact scan of one document as its kernel runs it (eval_scan_one): the tri-state (a
+// forest: of its whole fold code over res[]); res[p] receives each pattern's tri-state, from
+// the T bitmap the body wrote and, where that says not T, from the probe forest's results
+// (without a probe: static E, unsupported, else F, as stage_b() reads a bitmap).
+// 99 (no tri-state): the two disagree on a T bit.
 int ht_eval(void* h, const uint8_t* doc_in, uint32_t len, uint8_t* res, int32_t* err) {
     // (the device reads whole aligned blocks around a document: give the copy that slack)
     std::vector<uint8_t> buf(len + 32, 0);
     uint8_t* doc = buf.data() + 16;
     if (len) std::memcpy(doc, doc_in, len);
-    const uint8_t* blob = ((HtRuleset*)h)->c.blob.data();
+    const HtRuleset* rs = (const HtRuleset*)h;
+    const uint8_t* blob = rs->c.blob.data();
     const RulesetHdr* hd = (const RulesetHdr*)blob;
-    const Selector* sels = (const Selector*)(blob + hd->off_selectors);
-    const Component* comps = (const Component*)(blob + hd->off_components);
-    const Pattern* pats = (const Pattern*)(blob + hd->off_patterns);
-    const uint32_t* code = (const uint32_t*)(blob + hd->off_code);
-    const uint8_t* lits = blob + hd->off_literals;
-    for (uint32_t p = 0; p < hd->n_patterns; p++) {
-        ValueRef v{0, 0, T_NULL, 0};
-        if (pats[p].state == P_OK) {
-            const Selector& s = sels[pats[p].selector];
-            v = gj_get(doc, len, comps + s.comp_begin, s.comp_count, lits);
+    const uint32_t np = hd->n_patterns, slots = hd->pad1[0] ? hd->pad1[0] : 1u, stride = (np + 63u) / 64u + 1u;
+    std::vector<uint8_t> tri(slots, 0xEE), ptri(np ? np : 1u, 0xEE);
+    std::vector<int32_t> ep(slots, -7);
+    std::vector<uint64_t> bm(stride, ~0ull);
+    exact_one(blob, doc, len, -1, tri.data(), ep.data(), bm.data(), stride);
+    const bool probe = !rs->probe.blob.empty();
+    if (probe) exact_one(rs->probe.blob.data(), doc, len, -1, ptri.data(), nullptr, nullptr, 0);
+    for (uint32_t p = 0; p < np; p++) {
+        const uint64_t bit = 1ull << (p & 63);
+        const bool t = (bm[p >> 6] & bit) != 0;
+        if (probe) {
+            if (t != (ptri[p] == V_T)) return 99;
+            res[p] = ptri[p];
+        } else {
+            res[p] = t ? V_T : p < 128 && (hd->static_error[p >> 6] & bit) ? V_E
+                             : p < 128 && (hd->unsupported[p >> 6] & bit)  ? V_U
+                                                                           : V_F;
         }
-        if (pats[p].state == P_OK && v.esc == kValList) {  // a "#." list (the kernel's build_list)
-            static ModBufs mb;
-            const uint8_t* rd;
-            ValueRef rv;
-            res[p] = build_list(blob, sels[pats[p].selector], doc, v, mb, &rd, &rv)
-                         ? eval_pattern<true>(blob, pats[p], rd, rv)
-                         : (uint8_t)V_U;
-            continue;
-        }
-        if (pats[p].state == P_OK && sels[pats[p].selector].mod_count) {
-            static ModBufs mb;  // (the kernel's work-item scratch)
-            const uint8_t* rd;
-            ValueRef rv;
-            res[p] = apply_modifiers(blob, sels[pats[p].selector], doc, v, mb, &rd, &rv)
-                         ? eval_pattern<true>(blob, pats[p], rd, rv)
-                         : (uint8_t)V_U;
-            continue;
-        }
-        res[p] = eval_pattern<true>(blob, pats[p], doc, v);
     }
-    return run_fold(code, hd->n_code, [&](uint32_t p) { return res[p]; }, err);
+    if (bm[stride - 1]) return 99;  // (a word past the ruleset's patterns: zero)
+    if (hd->pad1[0])
+        return run_fold((const uint32_t*)(blob + hd->off_code), hd->n_code, [&](uint32_t p) { return res[p]; }, err);
+    *err = ep[0];
+    return tri[0];
+}
+
+// eval_scan_one for one document, the instance and the outputs named: mods 0 / 1 (-1: as the
+// launcher, by the ruleset), stride words of bitmap at bm (0: no bitmap), tri / err per tree
+void ht_eval_exact(void* h, const uint8_t* doc_in, uint32_t len, int mods, uint32_t stride, uint8_t* tri, int32_t* err,
+                   uint64_t* bm) {
+    std::vector<uint8_t> buf(len + 32, 0);
+    uint8_t* doc = buf.data() + 16;
+    if (len) std::memcpy(doc, doc_in, len);
+    exact_one(((HtRuleset*)h)->c.blob.data(), doc, len, mods, tri, err, stride ? bm : nullptr, stride);
 }
 
 // fault injection for the checker tests (tests/test_checker_sensitivity.py): 1 drops the
@@ -216,38 +266,39 @@ extern "C" uint64_t ht_flat_folds() { return g_flat_folds; }
 static uint64_t g_group_folds = 0;  // (the same for the group fold)
 extern "C" uint64_t ht_group_folds() { return g_group_folds; }
 
-// Stage B as the kernels run it (finish_request, ajx_stageb.h) for one request on its capture
-// row; dec / ring: the lean scan's decisions and the lane's span buffer, as its kernel passes
-// them. res[p] is read back from what it wrote (static E, unsupported, the T bitmap). Returns
-// -1 when it hands the request to the exact scan; 99 (no tri-state: the test's comparison
-// fails) when a tree's result is not the code interpreter's on res, or a bitmap word past the
-// ruleset's two was not zeroed; else the interpreter's tri-state of the fold code.
-static int stage_b(const uint8_t* blob, const uint8_t* d, uint64_t* row, const uint64_t* dec, uint8_t* ring,
-                   uint8_t* res, int32_t* err, bool count) {
+// What a single-pass body (scan_request + finish_request, lean_request) wrote for request 0:
+// res[p] is read back from it (static E, unsupported, the T bitmap of kOutStride words).
+// Returns 99 (no tri-state: the test's comparison fails) when a tree's result is not the
+// code interpreter's on res, or a bitmap word past the ruleset's two was not zeroed; else
+// the interpreter's tri-state of the fold code.
+constexpr uint32_t kOutStride = 4;  // (the ruleset's two words and two the writer must zero)
+struct Outs {
+    uint64_t bm[kOutStride];
+    std::vector<uint8_t> tri;
+    std::vector<int32_t> ep;
+    explicit Outs(const RulesetHdr* hd) : tri(hd->pad1[0] ? hd->pad1[0] : 1u, 0xEE), ep(tri.size(), -7) {
+        std::memset(bm, 0xFF, sizeof bm);
+    }
+};
+static int read_outs(const uint8_t* blob, const Outs& o, uint8_t* res, int32_t* err, bool count) {
     const RulesetHdr* hd = (const RulesetHdr*)blob;
-    const uint32_t nt = hd->pad1[0], slots = nt ? nt : 1u;
-    constexpr uint32_t kStride = 4;  // (the ruleset's two words and two the writer must zero)
-    uint64_t bm[kStride];
-    std::memset(bm, 0xFF, sizeof bm);
-    std::vector<uint8_t> tri(slots, 0xEE);
-    std::vector<int32_t> ep(slots, -7);
-    if (!finish_request(0, blob, d, RowRef(row), tri.data(), ep.data(), bm, kStride, dec, ring)) return -1;
-    if (bm[2] | bm[3]) return 99;
+    const uint32_t nt = hd->pad1[0];
+    if (o.bm[2] | o.bm[3]) return 99;
     for (uint32_t p = 0; p < hd->n_patterns; p++) {
         const uint64_t bit = 1ull << (p & 63);
         const uint32_t k = p >> 6;
-        res[p] = (hd->static_error[k] & bit) ? V_E : (hd->unsupported[k] & bit) ? V_U : (bm[k] & bit) ? V_T : V_F;
+        res[p] = (hd->static_error[k] & bit) ? V_E : (hd->unsupported[k] & bit) ? V_U : (o.bm[k] & bit) ? V_T : V_F;
     }
     if (count && (hd->flags & kFlagFlatFold)) g_flat_folds++;
     if (count && (hd->flags & kFlagGroupFold)) g_group_folds++;
     const uint32_t* code = (const uint32_t*)(blob + hd->off_code);
     const auto rp = [&](uint32_t p) { return res[p]; };
     const int whole = run_fold(code, hd->n_code, rp, err);
-    if (nt == 0) return tri[0] == whole && ep[0] == *err ? whole : 99;
+    if (nt == 0) return o.tri[0] == whole && o.ep[0] == *err ? whole : 99;
     const uint32_t* rc = (const uint32_t*)(blob + hd->pad1[1]);
     for (uint32_t k = 0; k < nt; k++) {  // (a forest: tree by tree)
         int32_t e;
-        if (tri[k] != run_fold(code + rc[2 * k], rc[2 * k + 1], rp, &e) || ep[k] != e) return 99;
+        if (o.tri[k] != run_fold(code + rc[2 * k], rc[2 * k + 1], rp, &e) || o.ep[k] != e) return 99;
     }
     return whole;
 }
@@ -257,17 +308,18 @@ extern "C" {
 // tri-state; res[p] receives each pattern's value. `mis` places the copy at that
 // misalignment (0..15) like an arbitrary arena offset.
 static int eval_single_pass(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err,
-                            bool ev, uint64_t* row_out);
+                            uint64_t* row_out);
 int ht_eval_fast(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err) {
-    return eval_single_pass(h, doc, len, mis, res, err, false, nullptr);
+    return eval_single_pass(h, doc, len, mis, res, err, nullptr);
 }
 // the token scanner with its capture row (row_out: 1 + n_selectors)
 int ht_eval_tok(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err,
                 uint64_t* row_out) {
-    return eval_single_pass(h, doc, len, mis, res, err, false, row_out);
+    return eval_single_pass(h, doc, len, mis, res, err, row_out);
 }
+// (ajx_scan_fused's request: scan_request, then finish_request)
 static int eval_single_pass(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err,
-                            bool ev, uint64_t* row_out) {
+                            uint64_t* row_out) {
     const uint8_t* blob = ((HtRuleset*)h)->c.blob.data();
     const RulesetHdr* hd = (const RulesetHdr*)blob;
     if (!(hd->flags & kFlagFastOk)) return -2;
@@ -276,19 +328,15 @@ static int eval_single_pass(void* h, const uint8_t* doc, uint32_t len, uint32_t 
     uint8_t* d = (uint8_t*)base + (mis & 15);
     std::memcpy(d, doc, len);
     std::vector<uint64_t> row(1 + hd->n_selectors, 0xDEADBEEFDEADBEEFull);
-    const uint32_t* a = (const uint32_t*)(d - mis);
     alignas(16) uint8_t ring_mem[128];
     std::memset(ring_mem, 0x5A, sizeof ring_mem);
     WinRing ring{ring_mem, 0u, 16u};
-    auto load = [&](uint32_t b, uint32_t nblk) -> Block16 {
-        if (b < nblk) return Block16{a[4 * b], a[4 * b + 1], a[4 * b + 2], a[4 * b + 3]};
-        return Block16{0, 0, 0, 0};
-    };
-    (void)ev;
-    const bool ok = scan_doc(blob, blob_tables(blob), d, len, row.data(), ring, load);
-    if (!ok) return -1;
+    const RowRef rr(row.data());
+    if (!scan_request(blob, d, len, rr, ring)) return row[0] == kRowSlow ? -1 : 99;
     if (row_out) std::memcpy(row_out, row.data(), row.size() * sizeof(uint64_t));
-    return stage_b(blob, d, row.data(), nullptr, nullptr, res, err, false);
+    Outs o(hd);
+    if (!finish_request(0, blob, d, rr, o.tri.data(), o.ep.data(), o.bm, kOutStride)) return -1;
+    return read_outs(blob, o, res, err, false);
 }
 }
 
@@ -319,36 +367,46 @@ extern "C" void ht_lean_last_dec(uint64_t* out) {
 // default when no caller reads the rows); 1 every record
 static uint32_t g_lean_keep = 1;
 extern "C" void ht_lean_keep(int keep) { g_lean_keep = keep ? 1u : 0u; }
+// arr = 1: the array-walking instance for every ruleset (the one ajx_scan_lean takes without
+// a staged blob, and the tenant kernel); 0: by the ruleset's kLeanArr, as launch_lean
+static bool g_lean_arr = false;
+extern "C" void ht_lean_arr(int arr) { g_lean_arr = arr != 0; }
 extern "C" int ht_eval_lean_row(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err,
                                 uint64_t* row_out) {
     const uint8_t* blob = ((HtRuleset*)h)->c.blob.data();
     const RulesetHdr* hd = (const RulesetHdr*)blob;
     if (!(hd->flags & kFlagFastOk)) return -2;
-    if (!lean::eligible(hd, len)) return -1;  // (as the kernels: empty or too long, the exact scan)
     std::vector<uint8_t> buf(len + 96, 0x7A);  // (neighbour bytes around the document)
     uintptr_t base = ((uintptr_t)buf.data() + 15) & ~(uintptr_t)15;
     uint8_t* d = (uint8_t*)base + (mis & 15);
     std::memcpy(d, doc, len);
     std::vector<uint64_t> row(1 + hd->n_selectors, 0xDEADBEEFDEADBEEFull);
-    const uint32_t* a = (const uint32_t*)(d - (mis & 15));
-    const uint32_t nb = (uint32_t)((buf.data() + buf.size() - (const uint8_t*)a) / 16);
+    const uint8_t* a = d - (mis & 15);
+    const uint32_t nb = (uint32_t)((buf.data() + buf.size() - a) / 16);
     // the wave's ring (chunk-major); this document's lane: mis * 5 (every lane offset used)
     static thread_local std::vector<uint8_t> ring_mem(lean::kRingBytesPerWave);
     std::memset(ring_mem.data(), 0x5A, ring_mem.size());
     const uint32_t nblk = (len + (mis & 15) + 15) / 16;
-    lean::CopyLoader ld{(const uint8_t*)a, nblk, nb, ring_mem.data() + ((mis * 5u) & 63u) * 16u};
+    lean::CopyLoader ld{a, nblk, nb, ring_mem.data() + ((mis * 5u) & 63u) * 16u};
     uint64_t dec[2] = {0, 0};
-    // (the instance the kernel takes for this ruleset: RulesetHdr::lean_feat)
-    const uint32_t m15 = (uint32_t)(mis & 15);
     const RowRef rr(row.data());
-    const bool ok = (hd->lean_feat & kLeanArr) ? lean::scan_doc<0, true>(blob, len, m15, rr, ld.lane_ring, ld, dec, g_lean_keep)
-                                               : lean::scan_doc<0, false>(blob, len, m15, rr, ld.lane_ring, ld, dec, g_lean_keep);
+    // (the kernels' request, lean_request; the instance launch_lean takes for this ruleset,
+    // RulesetHdr::lean_feat, or the array-walking one, ht_lean_arr; stage B's values from the
+    // lane's span buffer, as the kernel)
+    Outs o(hd);
+    uint32_t slow_count = 0, slow_id = ~0u;
+    if (g_lean_arr || (hd->lean_feat & kLeanArr))
+        lean_request<0, true>(0, 0, blob, d, len, rr, ld.lane_ring, ld.lane_ring, ld, g_lean_keep, &slow_count, &slow_id,
+                              o.tri.data(), o.ep.data(), o.bm, kOutStride, dec);
+    else
+        lean_request<0, false>(0, 0, blob, d, len, rr, ld.lane_ring, ld.lane_ring, ld, g_lean_keep, &slow_count,
+                               &slow_id, o.tri.data(), o.ep.data(), o.bm, kOutStride, dec);
     g_last_dec[0] = dec[0];
     g_last_dec[1] = dec[1];
-    if (!ok) return -1;
+    // handed to the exact scan: one list entry, the row marked
+    if (slow_count) return slow_count == 1 && slow_id == 0 && row[0] == kRowSlow ? -1 : 99;
     if (row_out) std::memcpy(row_out, row.data(), row.size() * sizeof(uint64_t));
-    // (values from the lane's span buffer, as the kernel)
-    return stage_b(blob, d, row.data(), dec, ld.lane_ring, res, err, true);
+    return read_outs(blob, o, res, err, true);
 }
 // tree_fold against the code interpreter for every forest tree with a TreeFold shape, on n
 // random 128-bit (T, U, static E) bitmaps: the number of differences (-1: no such tree)
@@ -442,89 +500,160 @@ extern "C" void ht_lean_counts(uint64_t* iters, uint64_t* subs) {
     *subs = lean::g_lean_subs;
 }
 
-// ---- the streaming scan (ajx_stream.h) on 64 host threads per wave (ajx_wave.h) ----
-#include "../../authorino_amd/csrc/ajx_stream.h"
+// ---- the streaming kernels' bodies (ajx_stream_body.h) on 64 host threads per wave (ajx_wave.h) ----
+#include "../../authorino_amd/csrc/ajx_stream_body.h"
 
-// every request of the batch through the stream kernel's code, one span (wave) at a time,
-// then stage B (finish_full) for those it hands over; out_slow[r] = 1 where the exact scan
-// decides request r (outputs unset), 2 where stage B decided it. mode 1: structure only
-// (out_tri[r] = proved). Returns -1 when the ruleset has no stream tables.
-extern "C" int ht_eval_stream(void* h, const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+// a 16-byte aligned copy of a ruleset's blob (as the device's)
+static std::vector<uint64_t> aligned_blob(const std::vector<uint8_t>& b) {
+    std::vector<uint64_t> v((b.size() + 7) / 8 + 2);
+    std::memcpy(v.data(), b.data(), b.size());
+    return v;
+}
+
+// Every request of the batch through the streaming kernels' code, as launch_eval_stream
+// runs them: stream_body per span (wave), the workgroup's LDS laid out as the kernel's; then
+// the stage-B list by stream_fin_list (fin) or stream_finish_entry, and, without merge_slow,
+// the exact scan over the slow list. out_slow[r] = 0 where the stream decided request r, 2
+// where stage B did, 1 where the exact scan did. mode 1: structure only (out_tri[r] = proved,
+// no lists).
+//   h2, set_of_req: a second ruleset (the MT instance: per = 1, request r under
+//     set_of_req[r] ? h2 : h); mt_wave_off: the room of a wave's own blob copy (0: the blob is
+//     read in place)
+//   keep_rows: every request's row is kept in rows (the wave layout, row_stride >= 5 + n_rec
+//     words; null: a buffer of the harness's)
+//   merge_slow: -1 as the launcher (per < 32 or MT), else 0 / 1
+//   lists (optional, 4 + 2 n words): [0] slow and [1] stage-B counts after the spans, [2] the
+//     final slow count, [3] the slow list's length; the stage-B list's entries from [4], the
+//     slow ids from [4 + n]
+// Returns -1 when a ruleset has no stream tables, -3 for a combination the launcher never makes.
+extern "C" int ht_eval_stream(void* h, void* h2, const uint32_t* set_of_req, uint32_t mt_wave_off,
+                              const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
                               uint8_t* out_tri, int32_t* out_err, uint64_t* out_bm, uint32_t stride, uint8_t* out_slow,
-                              int mode, uint32_t* out_dbg, uint32_t per) {
-    const std::vector<uint8_t>& blob_v = ((HtRuleset*)h)->c.blob;
-    const RulesetHdr* hd = (const RulesetHdr*)blob_v.data();
-    if (!hd->off_stream) return -1;
-    // (16-byte aligned copy, as in LDS)
-    std::vector<uint64_t> blob_buf((blob_v.size() + 7) / 8 + 2);
-    std::memcpy(blob_buf.data(), blob_v.data(), blob_v.size());
-    const uint8_t* blob = (const uint8_t*)blob_buf.data();
-    const uint32_t ns = reinterpret_cast<const StreamHdr*>(blob_v.data() + hd->off_stream)->n_rec;  // (records)
-    if (per == 0 || per > stream::kSpan) per = stream::kSpan;
-    const uint32_t spans = (n + per - 1) / per;
-    std::vector<uint64_t> wl(stream::lds_bytes(ns) / 8 + 2);
-    std::vector<uint64_t> stage_rows((size_t)n * (5 + ns));
-    std::vector<uint32_t> stage_list;
-    for (uint32_t span = 0; span < spans; span++) {
-        std::memset(wl.data(), 0xA5, wl.size() * 8);
-        stream::WaveLds& L = *reinterpret_cast<stream::WaveLds*>(wl.data());
-        uint64_t* rows = wl.data() + sizeof(stream::WaveLds) / 8;
-        std::mutex mu;
-        // (as the kernel's LAT instance for small batches: per < 32)
-        const bool lat = per < stream::kSpan;
-        wave::run_wave([&](uint32_t l) {
-            const uint64_t *rowp = nullptr, *dwp = nullptr;
-            const uint8_t* lds_doc = nullptr;
-            uint32_t res;
-            if (mode == 1)
-                res = stream::scan_span<1>(L, rows, blob, arena, offs, lens, n, span, per, l, out_tri, out_err,
-                                           out_bm, stride, &rowp, &dwp);
-            else
-                res = stream::scan_span<0>(L, rows, blob, arena, offs, lens, n, span, per, l, out_tri, out_err,
-                                           out_bm, stride, &rowp, &dwp, lat ? &lds_doc : nullptr);
-            const uint32_t r = span * per + l;
-            // (one request per wave: the whole wave runs its stage B, as the kernel does)
-            if (lat && per == 1 && wave::readlane(res == stream::R_STAGE_B && lds_doc ? 1u : 0u, 0) != 0) {
-                auto bcast = [](const void* q) {
-                    const uint64_t v = (uint64_t)(uintptr_t)q;
-                    return (uintptr_t)((uint64_t)wave::readlane((uint32_t)v, 0) |
-                                       ((uint64_t)wave::readlane((uint32_t)(v >> 32), 0) << 32));
-                };
-                const uint8_t* d0 = reinterpret_cast<const uint8_t*>(bcast(lds_doc));
-                uint64_t* row0 = reinterpret_cast<uint64_t*>(bcast(rowp));
-                const uint64_t* dw0 = reinterpret_cast<const uint64_t*>(bcast(dwp));
-                const bool ok = stream::finish_full<true>(span, blob, d0, lens[span], RowRef(row0), out_tri, out_err,
-                                                          out_bm, stride, dw0);
-                if (l == 0) out_slow[span] = ok ? 2 : 1;
-                return;
-            }
-            if (l >= per || r >= n) return;
-            out_slow[r] = res == stream::R_SLOW ? 1 : 0;
-            if (res == stream::R_STAGE_B && lds_doc) {  // stage B on the ring's copy of the document
-                const bool ok = stream::finish_full(r, blob, lds_doc, lens[r], RowRef(const_cast<uint64_t*>(rowp)),
-                                                    out_tri, out_err, out_bm, stride, dwp);
-                out_slow[r] = ok ? 2 : 1;
-                return;
-            }
-            if (res == stream::R_STAGE_B) {
-                uint64_t* o = stage_rows.data() + (size_t)r * (5 + ns);
-                std::memcpy(o, rowp, (1 + ns) * 8);
-                std::memcpy(o + 1 + ns, dwp, 4 * 8);
-                std::lock_guard<std::mutex> g(mu);
-                stage_list.push_back(r);
-            }
-            if (out_dbg) {  // (bad position, root close)
-                out_dbg[2 * r] = L.bad[l];
-                out_dbg[2 * r + 1] = L.root_end[l];
-            }
-        });
+                              int mode, uint32_t* out_dbg, uint32_t per, uint32_t keep_rows, int merge_slow, int fin,
+                              uint64_t* rows_io, uint32_t row_stride, uint32_t* lists) {
+    const bool mt = h2 != nullptr;
+    std::vector<uint64_t> blobs[2] = {aligned_blob(((HtRuleset*)h)->c.blob),
+                                      aligned_blob(((HtRuleset*)(mt ? h2 : h))->c.blob)};
+    const uint8_t* sets[2] = {(const uint8_t*)blobs[0].data(), (const uint8_t*)blobs[1].data()};
+    uint32_t ns = 0, blob_bytes = 0;
+    bool mods = false;
+    for (const uint8_t* b : sets) {
+        const RulesetHdr* hd = (const RulesetHdr*)b;
+        if (!hd->off_stream) return -1;
+        const uint32_t k = reinterpret_cast<const StreamHdr*>(b + hd->off_stream)->n_rec;  // (records)
+        ns = k > ns ? k : ns;
+        blob_bytes = hd->total_bytes > blob_bytes ? hd->total_bytes : blob_bytes;
+        mods = mods || hd->n_modifiers != 0 || (hd->flags & kFlagBufs) != 0;
     }
-    for (uint32_t r : stage_list) {
-        RowRef row(stage_rows.data() + (size_t)r * (5 + ns));
-        const bool ok = stream::finish_full(r, blob, arena + offs[r], lens[r], row, out_tri, out_err, out_bm, stride);
-        out_slow[r] = ok ? 2 : 1;
+    if (mt) per = 1;
+    if (per == 0 || per > stream::kSpan) per = stream::kSpan;
+    const bool merge = merge_slow < 0 ? (mt || per < stream::kSpan) : merge_slow != 0;
+    const bool lat = merge && !keep_rows;  // (the kernel's LAT instance, as the launcher picks it)
+    if ((mt && (mode != 0 || !merge)) || (fin && (!lat || mods))) return -3;
+    // the workgroup's dynamic LDS: [blob copy] [per wave: WaveLds, rows]; MT: per wave
+    // [room for its blob] [WaveLds, rows]
+    constexpr uint32_t kWaves = 4;
+    uint32_t wave_off = mt ? (mt_wave_off + 15u) & ~15u : (blob_bytes + 15u) & ~15u;
+    uint32_t wave_bytes = ((stream::lds_bytes(ns) + 15u) & ~15u) + (mt ? wave_off : 0u);
+    std::vector<uint64_t> dyn_mem(((mt ? 0u : wave_off) + kWaves * wave_bytes) / 8 + 2);
+    uint8_t* dyn = (uint8_t*)dyn_mem.data();
+    if (row_stride == 0) row_stride = 5 + ns;
+    if (row_stride < 5 + ns) return -3;
+    std::vector<uint64_t> own_rows(rows_io ? 0 : (size_t)((n + 63u) & ~63u) * row_stride);
+    uint64_t* rows = rows_io ? rows_io : own_rows.data();
+    // the counters and the slow ids in one buffer, the stage-B list in another (the workspace's)
+    std::vector<uint32_t> slow_buf(n + kStreamCounterWords, 0), stage_list(n + 1, 0);
+    StreamCounters* ctr = stream_counters(slow_buf.data());
+    uint32_t* slow_ids = stream_slow_ids(slow_buf.data());
+    const uint32_t* sor = mt ? set_of_req : nullptr;
+    const uint32_t spans = (n + per - 1) / per;
+    const uint32_t keep = keep_rows ? kKeepRows : 0u;
+    for (uint32_t span = 0; span < spans; span++) {
+        const uint32_t w = span % kWaves;
+        std::memset(dyn, 0xA5, dyn_mem.size() * 8);
+        if (!mt) std::memcpy(dyn, sets[0], blob_bytes);  // (stage_blob<true>)
+        wave::run_wave([&](uint32_t l) {
+            uint32_t d;
+#define AJX_BODY(M, T, LT)                                                                                          \
+    stream_body<M, T, LT>(sets, sor, arena, offs, lens, n, ctr, slow_ids, stage_list.data(), out_tri, out_err, out_bm,  \
+                          stride, wave_off, wave_bytes, rows, row_stride, keep, per, merge ? 1u : 0u, dyn, w, l, span,  \
+                          mt ? nullptr : dyn, 0ull)
+            if (mode == 1) d = AJX_BODY(1, false, false);
+            else if (mt) d = lat ? AJX_BODY(0, true, true) : AJX_BODY(0, true, false);
+            else d = lat ? AJX_BODY(0, false, true) : AJX_BODY(0, false, false);
+#undef AJX_BODY
+            const uint32_t r = span * per + l;
+            if (d != kDispNone) out_slow[r] = (uint8_t)d;
+        });
+        if (out_dbg) {  // (bad position, root close)
+            const stream::WaveLds& L =
+                *reinterpret_cast<const stream::WaveLds*>(mt ? dyn + w * wave_bytes + wave_off : dyn + wave_off + w * wave_bytes);
+            for (uint32_t l = 0; l < per && span * per + l < n; l++) {
+                out_dbg[2 * (span * per + l)] = L.bad[l];
+                out_dbg[2 * (span * per + l) + 1] = L.root_end[l];
+            }
+        }
+    }
+    if (lists) {
+        lists[0] = ctr->slow;
+        lists[1] = ctr->stage_b;
+        for (uint32_t i = 0; i < ctr->stage_b; i++) lists[4 + i] = stage_list[i];
+    }
+    if (mode != 0) return 0;
+    // the stage-B list, an entry at a time: where stage B could not decide the request the
+    // slow count moved (and, without merge_slow, the slow list got it)
+    const uint32_t cnt = ctr->stage_b;
+    for (uint32_t i = 0; i < cnt; i++) {
+        const uint32_t before = ctr->slow, e = stage_list[i];
+        if (fin) {  // (lane 0's share of a one-entry list)
+            if (mt) stream_fin_list<true>(sets, sor, arena, offs, lens, 1u, ctr, &stage_list[i], out_tri, out_err, out_bm, stride, rows, row_stride, 0u);
+            else stream_fin_list<false>(sets, sor, arena, offs, lens, 1u, ctr, &stage_list[i], out_tri, out_err, out_bm, stride, rows, row_stride, 0u);
+        } else {
+#define AJX_ENTRY(T, X)                                                                                             \
+    stream_finish_entry<T, X>(e, sets[0], sets, sor, arena, offs, lens, rows, row_stride, ctr, slow_ids, out_tri, out_err, \
+                              out_bm, stride)
+            if (mt && mods) AJX_ENTRY(true, 2);
+            else if (mt) AJX_ENTRY(true, 1);
+            else if (merge && mods) AJX_ENTRY(false, 2);
+            else if (merge) AJX_ENTRY(false, 1);
+            else AJX_ENTRY(false, 0);
+#undef AJX_ENTRY
+        }
+        if ((e & kStageExact) || ctr->slow != before) out_slow[e & ~kStageExact] = 1;
+    }
+    if (!merge) {  // (ajx_eval_scan_list over the slow list)
+        const uint32_t trees = ((const RulesetHdr*)sets[0])->pad1[0];
+        const uint32_t nt = trees ? trees : 1u;
+        for (uint32_t i = 0; i < ctr->slow; i++) {
+            const uint32_t r = slow_ids[i];
+            exact_one(sets[0], arena + offs[r], lens[r], mods, out_tri + (size_t)r * nt, out_err + (size_t)r * nt,
+                      out_bm ? out_bm + (size_t)r * stride : nullptr, stride);
+        }
+    }
+    if (lists) {
+        lists[2] = ctr->slow;
+        lists[3] = merge ? 0u : ctr->slow;  // (ids on the slow list: with merge_slow it only counts)
+        for (uint32_t i = 0; i < lists[3]; i++) lists[4 + n + i] = slow_ids[i];
     }
     return 0;
+}
+
+// select_request (the select kernel's body) for every request of a batch under one ruleset:
+// out[n][stride][3]; rows (or null: the exact Get) in the wave layout (wave_rows) or one per
+// request; text (or null: the instance without TEXT) of text_stride bytes per request
+extern "C" void ht_select_rows(void* h, const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                               uint32_t* out, uint32_t stride, const uint64_t* rows, uint32_t row_stride, uint32_t p0,
+                               uint32_t wave_rows, uint8_t* text, uint32_t text_stride) {
+    std::vector<uint64_t> blob = aligned_blob(((HtRuleset*)h)->c.blob);
+    const uint8_t* sets[1] = {(const uint8_t*)blob.data()};
+    for (uint32_t r = 0; r < n; r++) {
+        if (text)
+            select_request<true>(r, r, sets, nullptr, arena, offs, lens, out, stride, rows, row_stride, p0, wave_rows, text,
+                                 text_stride);
+        else
+            select_request<false>(r, r, sets, nullptr, arena, offs, lens, out, stride, rows, row_stride, p0, wave_rows,
+                                  nullptr, 0u);
+    }
 }
 
 // the launch plan (ajx_plan.h): which kernel a batch gets, as the library decides it

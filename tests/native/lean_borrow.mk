@@ -6,7 +6,7 @@
 CXX ?= g++
 CSRC = ../../authorino_amd/csrc
 CXXFLAGS ?= -O1 -g -fPIC -Wall -Wno-unused-function -Wno-unknown-pragmas
-HDRS = $(CSRC)/ajx_device.h $(CSRC)/ajx_float.h $(CSRC)/ajx_modifiers.h $(CSRC)/ajx_unicode.h $(CSRC)/ajx_fast.h $(CSRC)/ajx_stageb.h $(CSRC)/ajx_lean.h $(CSRC)/ajx_lean_cls.h $(CSRC)/ajx_blob.h $(CSRC)/ajx_compiler.h $(CSRC)/ajx_regex.h $(CSRC)/ajx_stream.h $(CSRC)/ajx_wave.h $(CSRC)/ajx_plan.h
+HDRS = $(CSRC)/ajx_device.h $(CSRC)/ajx_float.h $(CSRC)/ajx_modifiers.h $(CSRC)/ajx_unicode.h $(CSRC)/ajx_fast.h $(CSRC)/ajx_stageb.h $(CSRC)/ajx_lean.h $(CSRC)/ajx_lean_cls.h $(CSRC)/ajx_blob.h $(CSRC)/ajx_compiler.h $(CSRC)/ajx_regex.h $(CSRC)/ajx_stream.h $(CSRC)/ajx_wave.h $(CSRC)/ajx_plan.h $(CSRC)/ajx_request.h $(CSRC)/ajx_stream_body.h
 SRCS = lean_borrow_host.cpp $(CSRC)/ajx_compiler.cpp $(CSRC)/ajx_regex.cpp
 all: libajx_leanborrow.so
 # (linked to a temporary name and renamed into place: parallel test workers may rebuild a

@@ -22,6 +22,10 @@ void ht_free(void* h);
 int ht_eval(void* h, const uint8_t* doc, uint32_t len, uint8_t* res, int32_t* err);
 int ht_eval_fast(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err);
 int ht_eval_lean(void* h, const uint8_t* doc, uint32_t len, uint32_t mis, uint8_t* res, int32_t* err);
+int ht_eval_stream(void* h, void* h2, const uint32_t* set_of_req, uint32_t mt_wave_off, const uint8_t* arena,
+                   const uint64_t* offs, const uint32_t* lens, uint32_t n, uint8_t* out_tri, int32_t* out_err,
+                   uint64_t* out_bm, uint32_t stride, uint8_t* out_slow, int mode, uint32_t* out_dbg, uint32_t per,
+                   uint32_t keep_rows, int merge_slow, int fin, uint64_t* rows_io, uint32_t row_stride, uint32_t* lists);
 }
 
 static std::mt19937_64 rng;
@@ -112,7 +116,7 @@ static std::string rand_selector() {
 int main(int argc, char** argv) {
     const long iters = argc > 1 ? atol(argv[1]) : 300;
     rng.seed(argc > 2 ? (uint64_t)atoll(argv[2]) : 7);
-    long docs = 0, fast_decided = 0, lean_decided = 0, bad = 0;
+    long docs = 0, fast_decided = 0, lean_decided = 0, stream_reqs = 0, bad = 0;
     for (long it = 0; it < iters; it++) {
         const int np = 1 + (int)rnd(8);
         std::vector<std::string> sels(np), vals(np);
@@ -139,6 +143,12 @@ int main(int argc, char** argv) {
         char err[256];
         void* h = ht_compile(&tree, st.data(), err, sizeof err, &rc);
         if (!h) continue;
+        // (every 100th ruleset: its documents as one batch through the streaming kernels' bodies)
+        const bool stream = it % 100 == 0;
+        std::string arena;
+        std::vector<uint64_t> offs;
+        std::vector<uint32_t> lens;
+        std::vector<int> want;
         for (int k = 0; k < 12; k++) {
             std::string d = rand_doc();
             if (rnd(3) == 0) d = mutate(d);
@@ -148,6 +158,12 @@ int main(int argc, char** argv) {
             const int t1 = ht_eval_fast(h, (const uint8_t*)d.data(), (uint32_t)d.size(), (uint32_t)rnd(16), r1.data(), &e1);
             const int t2 = ht_eval_lean(h, (const uint8_t*)d.data(), (uint32_t)d.size(), (uint32_t)rnd(16), r2.data(), &e2);
             docs++;
+            if (stream) {
+                offs.push_back(arena.size());
+                lens.push_back((uint32_t)d.size());
+                arena += d;
+                want.push_back(std::find(r0.begin(), r0.end(), (uint8_t)3) == r0.end() ? t0 : -1);
+            }
             if (t1 >= 0) {
                 fast_decided++;
                 if (t1 != t0 || r1 != r0) {
@@ -163,8 +179,32 @@ int main(int argc, char** argv) {
                 }
             }
         }
+        if (stream) {
+            // one request per wave (the small-batch dispatch, its list by either function), then
+            // four per wave without merge_slow (the slow list and the exact scan over it)
+            const uint32_t n = (uint32_t)lens.size();
+            arena.append(64, '\0');
+            for (int v = 0; v < 3; v++) {
+                std::vector<uint8_t> tri(n, 0xEE), slow(n, 0);
+                std::vector<int32_t> ep(n, -7);
+                std::vector<uint64_t> bm(2 * n, ~0ull);
+                const int rc = ht_eval_stream(h, nullptr, nullptr, 0, (const uint8_t*)arena.data(), offs.data(),
+                                              lens.data(), n, tri.data(), ep.data(), bm.data(), 2, slow.data(), 0, nullptr,
+                                              v < 2 ? 1u : 4u, 0, v < 2 ? -1 : 0, v == 0, nullptr, 0, nullptr);
+                if (rc == -1) break;    // (no stream tables)
+                if (rc < 0) continue;  // (modifier buffers: the last wave runs no list)
+                for (uint32_t r = 0; r < n; r++) {
+                    stream_reqs++;
+                    if (want[r] >= 0 && tri[r] != want[r]) {
+                        if (bad < 10) printf("STREAM MISMATCH variant %d doc=%s\n", v, arena.substr(offs[r], lens[r]).c_str());
+                        bad++;
+                    }
+                }
+            }
+        }
         ht_free(h);
     }
-    printf("docs %ld fast_decided %ld lean_decided %ld mismatches %ld\n", docs, fast_decided, lean_decided, bad);
+    printf("docs %ld fast_decided %ld lean_decided %ld stream_requests %ld mismatches %ld\n", docs, fast_decided,
+           lean_decided, stream_reqs, bad);
     return bad ? 1 : 0;
 }

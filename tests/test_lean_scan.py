@@ -46,14 +46,19 @@ def _chain(n):
     return nodes, root
 
 
-@pytest.fixture(params=[True, False], ids=["keep_rows", "needed_rows"])
+@pytest.fixture(params=[(True, False), (False, False), (True, True), (False, True)],
+                ids=["keep_rows", "needed_rows", "keep_rows-arr", "needed_rows-arr"])
 def keep(request):
     """Both capture-row modes of the lean scan: rows a caller reads (the records of its
     selectors, kEagerKeep, as well) and only what stage B needs (values decided in the scan
-    leave no record)."""
-    H.lean_keep(request.param)
-    yield request.param
+    leave no record). Each through both instances of the kernels' request (lean_request):
+    the one the launcher picks by the ruleset's kLeanArr, and (-arr) the array-walking one,
+    which the kernel without a staged blob and the tenant kernel run for every ruleset."""
+    H.lean_keep(request.param[0])
+    H.lean_arr(request.param[1])
+    yield request.param[0]
     H.lean_keep(True)
+    H.lean_arr(False)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3, 4, 5])
