@@ -545,6 +545,68 @@ int compile_core(const authjx_tree* tree, const std::vector<int32_t>& roots, boo
         return AUTHJX_EINVAL;
     }
 
+    // ---- the regexes, compiled once here: the fold's order below reads their status ----
+    struct Rx {
+        RegexStatus st = RX_OK;
+        RegexDfa dfa;
+        std::string err;
+        bool go_compiles = false;
+    };
+    std::vector<Rx> rx(np);
+    // 0: decided on the device (T, F, or undecided at run time: never an error), 1: unsupported
+    // but T or F in Go (a regexp over the DFA limits), 2: an error or possibly one
+    std::vector<uint8_t> pat_class(np, 0);
+    for (uint32_t i = 0; i < np; i++) {
+        const authjx_pattern& ap = tree->patterns[i];
+        if (ap.op < AUTHJX_OP_EQ || ap.op > AUTHJX_OP_MATCHES) { pat_class[i] = 2; continue; }
+        if (ap.op != AUTHJX_OP_MATCHES) continue;  // (an unsupported selector: 2, set where it is found out)
+        Rx& r = rx[i];
+        r.st = compile_go_regex(std::string(ap.value ? ap.value : "", ap.value_len), &r.dfa, &r.err, &r.go_compiles);
+        pat_class[i] = r.st == RX_OK ? 0 : r.go_compiles ? 1 : 2;
+    }
+    // Go's And / Or return the first operand that is an error or decides them. An operand that
+    // is unsupported but never an error (class 1) therefore commutes with the decided operands
+    // after it: it moves behind them, up to the first operand that may be an error, so that
+    // Or(<regexp too large>, w eq "z") is T where w is "z" instead of UNDECIDED. (The fold
+    // itself treats every undecided operand as a possible error.) Selectors are not parsed yet:
+    // an operand moves only past patterns whose selector holds plain keys (no modifier, query,
+    // '#', wildcard or escape: such a selector always compiles).
+    auto plain_selector = [&](uint32_t i) {
+        const authjx_pattern& ap = tree->patterns[i];
+        for (uint32_t k = 0; k < ap.selector_len; k++) {
+            const unsigned char c = (unsigned char)ap.selector[k];
+            if (!(c == '.' || c == '_' || c == '-' || (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z')))
+                return false;
+        }
+        return ap.selector_len != 0;
+    };
+    std::function<bool(const NormNode&)> decided = [&](const NormNode& n) {
+        if (n.kind == 2) return pat_class[(size_t)n.pattern] == 0 && plain_selector((uint32_t)n.pattern);
+        if (n.kind >= 3) return true;
+        for (const NormNode& c : n.kids)
+            if (!decided(c)) return false;
+        return true;
+    };
+    std::function<void(NormNode&)> reorder = [&](NormNode& n) {
+        if (n.kind > 1) return;
+        std::vector<NormNode> kids, waiting;
+        for (NormNode& c : n.kids) {
+            reorder(c);
+            if (c.kind == 2 && pat_class[(size_t)c.pattern] == 1) {
+                waiting.push_back(std::move(c));
+            } else if (decided(c)) {
+                kids.push_back(std::move(c));
+            } else {
+                for (NormNode& w : waiting) kids.push_back(std::move(w));
+                waiting.clear();
+                kids.push_back(std::move(c));
+            }
+        }
+        for (NormNode& w : waiting) kids.push_back(std::move(w));
+        n.kids = std::move(kids);
+    };
+    for (NormNode& rn : normed) reorder(rn);
+
     std::vector<uint32_t> code;
     uint32_t max_depth = 0;
     std::function<void(const NormNode&, uint32_t)> emit = [&](const NormNode& n, uint32_t depth) {
@@ -604,9 +666,9 @@ int compile_core(const authjx_tree* tree, const std::vector<int32_t>& roots, boo
             continue;
         }
         if (ap.op == AUTHJX_OP_MATCHES) {
-            RegexDfa dfa;
-            std::string rerr;
-            RegexStatus st = compile_go_regex(val, &dfa, &rerr);
+            RegexDfa& dfa = rx[i].dfa;
+            const std::string& rerr = rx[i].err;
+            const RegexStatus st = rx[i].st;
             if (st == RX_ERROR) {
                 p.state = P_STATIC_E;
                 out->pattern_status[i] = AUTHJX_PAT_STATIC_ERROR;

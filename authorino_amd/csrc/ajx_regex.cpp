@@ -485,8 +485,9 @@ class Parser {
         return e + 2 - i;
     }
 
-    size_t class_char(size_t i, uint32_t* r) const {
-        if (i >= whole_.size()) throw ParseError{"missing closing ]", whole_};
+    // (parse.go parseClassChar: the error's text is the class from its '[' to the end)
+    size_t class_char(size_t i, uint32_t* r, size_t cls) const {
+        if (i >= whole_.size()) throw ParseError{"missing closing ]", whole_.substr(cls)};
         if (whole_[i] == '\\') return parse_escape(i, r);
         return i + next_rune(i, r);
     }
@@ -512,10 +513,10 @@ class Parser {
             if (perl_class(i, &nd->set, &e)) { i = e; continue; }
             size_t rng = i;
             uint32_t lo, hi;
-            i = class_char(i, &lo);
+            i = class_char(i, &lo, start);
             hi = lo;
             if (s.size() >= i + 2 && s[i] == '-' && s[i + 1] != ']') {
-                i = class_char(i + 1, &hi);
+                i = class_char(i + 1, &hi, start);
                 if (hi < lo) throw ParseError{"invalid character class range", s.substr(rng, i - rng)};
             }
             add_range(nd->set, lo, hi, flags_);
@@ -929,7 +930,8 @@ RegexStatus build_dfa(const Prog& p, RegexDfa* out) {
 
 }  // namespace
 
-RegexStatus compile_go_regex(const std::string& pat, RegexDfa* out, std::string* err) {
+RegexStatus compile_go_regex(const std::string& pat, RegexDfa* out, std::string* err, bool* go_compiles) {
+    if (go_compiles) *go_compiles = false;
     try {
         Parser ps(pat);
         Node* root = ps.parse();
@@ -944,6 +946,9 @@ RegexStatus compile_go_regex(const std::string& pat, RegexDfa* out, std::string*
         }
         RegexStatus st = build_dfa(prog, out);
         if (st != RX_OK && err) *err = "regexp DFA exceeds the device limits";
+        // (a level of nesting takes a byte of the pattern or more; the program is under 300,000
+        // instructions here)
+        if (st == RX_UNSUPPORTED && go_compiles) *go_compiles = pat.size() <= 900;
         return st;
     } catch (const ParseError& e) {
         if (err) *err = "error parsing regexp: " + e.code + ": `" + e.expr + "`";

@@ -23,7 +23,10 @@ enum RegexStatus { RX_OK = 0, RX_ERROR = 1, RX_UNSUPPORTED = 2 };
 // Parses `pat` with Go 1.21 regexp.Compile rules (Perl flags). On a syntax error returns
 // RX_ERROR with Go's message in *err ("error parsing regexp: ..."). Syntax the device
 // compiler does not handle (\p{..} Unicode groups, case folding of non-ASCII runes,
-// DFAs over kMaxDfaStates states) returns RX_UNSUPPORTED.
-RegexStatus compile_go_regex(const std::string& pat, RegexDfa* out, std::string* err);
+// DFAs over kMaxDfaStates states) returns RX_UNSUPPORTED. *go_compiles (optional) is set
+// when an RX_UNSUPPORTED pattern is known to compile in Go: it parsed, only the DFA's size
+// stopped it, and it is far inside Go's own limits (parse.go checkLimits: 1000 levels of
+// nesting, 3.3 M instructions) — its Matches is T or F, never an error.
+RegexStatus compile_go_regex(const std::string& pat, RegexDfa* out, std::string* err, bool* go_compiles = nullptr);
 
 }  // namespace ajx

@@ -588,6 +588,7 @@ static node* parse(parser* p, const char* s, size_t n) {
     p->wlen = n;
     size_t i = 0;
     int last_repeat = 0;
+    size_t last_at = 0; /* where the previous operator began (parse.go's lastRepeat) */
     while (i < n) {
         int repeat = 0;
         char c = s[i];
@@ -688,7 +689,8 @@ static node* parse(parser* p, const char* s, size_t n) {
                 size_t after = i + tl;
                 if (after < n && s[after] == '?') after++;
                 if (last_repeat) {
-                    fail(p, "invalid nested repetition operator", s + i, after - i);
+                    /* repeat(): Expr is lastRepeat[:len(lastRepeat)-len(after)], both operators */
+                    fail(p, "invalid nested repetition operator", s + last_at, after - last_at);
                     return NULL;
                 }
                 if (p->n == 0 || p->st[p->n - 1]->op >= P_LPAREN) {
@@ -706,6 +708,7 @@ static node* parse(parser* p, const char* s, size_t n) {
                     return NULL;
                 }
                 repeat = 1;
+                last_at = i;
                 i = after;
                 break;
             }

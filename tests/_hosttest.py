@@ -133,6 +133,22 @@ class HostRuleset:
         t = lib().ht_eval(self._h, d, len(d), res, C.byref(err))
         return t, err.value, list(res)[: self.n]
 
+    @property
+    def blob_size(self) -> int:
+        """Bytes of the compiled blob (what kMaxSharedBlobBytes is compared with)."""
+        L = lib()
+        L.ht_blob_size.argtypes = [C.c_void_p]
+        L.ht_blob_size.restype = C.c_uint32
+        return L.ht_blob_size(self._h)
+
+    @property
+    def blob_hot_bytes(self) -> int:
+        """RulesetHdr.hot_bytes: the prefix the tenant kernel stages (kMaxTenantStageBytes)."""
+        L = lib()
+        L.ht_blob_hot_bytes.argtypes = [C.c_void_p]
+        L.ht_blob_hot_bytes.restype = C.c_uint32
+        return L.ht_blob_hot_bytes(self._h)
+
     def select_value(self, p, doc, text, used):
         """select_value of pattern p's selector (the select kernel's TEXT instance): (rc,
         [start, len, type | esc << 8], used) with built text appended to `text` (bytearray)."""

@@ -44,6 +44,16 @@ GO_121_COMPILE_ERRORS = [
     ("[a", "missing closing ]: `[a`"),
     ("[not-a-regex", "invalid character class range: `t-a`"),  # (the range fails before the end)
     ("\\", "trailing backslash at end of expression: ``"),
+    # parseClassChar(s, wholeClass): ErrMissingBracket's text is the class from its '[', not
+    # the whole expression (found by tests/test_regex_diff.py's mutations)
+    ("a[b", "missing closing ]: `[b`"),
+    ("(?:x[^a-c)|K", "missing closing ]: `[^a-c)|K`"),
+    ("x[a-", "missing closing ]: `[a-`"),
+    # repeat(): ErrInvalidRepeatOp's text is lastRepeat[:len(lastRepeat)-len(after)]: from the
+    # first operator through the second, a lazy `?` of either included
+    ("a??*", "invalid nested repetition operator: `??*`"),
+    ("a*?+?", "invalid nested repetition operator: `*?+?`"),
+    ("a*{2}", "invalid nested repetition operator: `*{2}`"),
 ]
 
 
@@ -59,6 +69,15 @@ def test_oracle_decides_compile_errors_e(pat, msg):
     pats = [("a", 5, pat)]
     rs = O.Ruleset(pats, [(0, -1, -1, 0)], 0)
     assert rs.pattern(0, b'{"a":"x"}') == O.E
+
+
+@pytest.mark.parametrize("pat,msg", GO_121_COMPILE_ERRORS)
+def test_oracle_compile_error_text(pat, msg):
+    """The oracle's own text (tests/test_regex_diff.py compares the two on generated
+    patterns: both must then be Go's)."""
+    r = O.Regex(pat)
+    assert not r._h and not r.unsupported
+    assert r.error == "error parsing regexp: " + msg
 
 
 @pytest.mark.parametrize("pat", ["\\Q", "(?P<n>a)(?P<n>b)", "a{1000}", "x{0,1000}", "(?i)abc", "[[:alpha:]]"])
