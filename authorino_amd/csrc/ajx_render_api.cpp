@@ -1,43 +1,20 @@
 // ajx_render_api.cpp — the render entry points of the C-ABI (include/authjx.h): render
 // programs resident in HBM and the batch calls that run them (ajx_render.hip). A
 // translation unit of its own: ajx_api.cpp does not reference it.
-#include <hip/hip_runtime.h>
-
 #include <cstdio>
 #include <string>
-#include <vector>
 
+#include "ajx_host.h"
 #include "ajx_render_api.h"
 #include "ajx_render_prog.h"
 
 struct authjx_render {
     int device = 0;
-    uint8_t* d_prog = nullptr;
+    ajx::DeviceBuf d_prog;
     uint32_t n_outputs = 0, n_slots = 0;
 };
 
 static_assert(sizeof(authjx_rendered) == 12, "authjx_rendered is three u32 words on the device");
-
-namespace {
-
-#define RENDER_HIP_OK(x)                                  \
-    do {                                                  \
-        if ((x) != hipSuccess) {                          \
-            (void)hipGetLastError();                      \
-            return AUTHJX_EDEVICE;                        \
-        }                                                 \
-    } while (0)
-
-size_t up256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
-struct DeviceBuf {
-    uint8_t* p = nullptr;
-    ~DeviceBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-}  // namespace
 
 int authjx_render_compile(authjx_ctx* ctx, const authjx_render_output* outs, uint32_t n_outputs, uint32_t n_slots,
                           authjx_render** out, char* errbuf, size_t errcap) {
@@ -52,13 +29,12 @@ int authjx_render_compile(authjx_ctx* ctx, const authjx_render_output* outs, uin
         return rc;
     }
     authjx_render* p = new authjx_render();
-    p->device = ajx_ctx_device(ctx);
+    p->device = ctx->device;
     p->n_outputs = n_outputs;
     p->n_slots = n_slots;
-    if (hipSetDevice(p->device) != hipSuccess || hipMalloc(&p->d_prog, blob.size()) != hipSuccess ||
-        hipMemcpy(p->d_prog, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipSetDevice(p->device) != hipSuccess || p->d_prog.reserve(blob.size()) != hipSuccess ||
+        hipMemcpy(p->d_prog.data(), blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        if (p->d_prog) (void)hipFree(p->d_prog);
         delete p;
         return AUTHJX_EDEVICE;
     }
@@ -68,11 +44,8 @@ int authjx_render_compile(authjx_ctx* ctx, const authjx_render_output* outs, uin
 
 void authjx_render_free(authjx_render* prog) {
     if (!prog) return;
-    if (prog->d_prog) {
-        (void)hipSetDevice(prog->device);
-        (void)hipFree(prog->d_prog);  // (waits for the kernels that read it)
-    }
-    delete prog;
+    if (prog->d_prog.data()) (void)hipSetDevice(prog->device);
+    delete prog;  // (freeing the program waits for the kernels that read it)
 }
 
 uint32_t authjx_render_outputs(const authjx_render* prog) { return prog ? prog->n_outputs : 0u; }
@@ -86,12 +59,12 @@ int authjx_render_batch_device(authjx_ctx* ctx, const authjx_render* prog, const
     if (values_stride < prog->n_slots || out_stride == 0 || out_stride % 16u != 0) return AUTHJX_EINVAL;
     if (n && (!d_arena || !d_offs || !d_lens || !d_out_text || !d_out || (prog->n_slots && !d_values)))
         return AUTHJX_EINVAL;
-    if (((uintptr_t)d_out_text & 15u) != 0 || prog->device != ajx_ctx_device(ctx)) return AUTHJX_EINVAL;
-    RENDER_HIP_OK(hipSetDevice(prog->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ajx_ctx_stream(ctx);
-    RENDER_HIP_OK(ajx::launch_render(prog->d_prog, prog->n_outputs, d_arena, d_offs, d_lens, n,
-                                     reinterpret_cast<const uint32_t*>(d_values), values_stride, d_text, text_stride,
-                                     d_out_text, out_stride, reinterpret_cast<uint32_t*>(d_out), s));
+    if (((uintptr_t)d_out_text & 15u) != 0 || prog->device != ctx->device) return AUTHJX_EINVAL;
+    HIP_OK(hipSetDevice(prog->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    HIP_OK(ajx::launch_render(prog->d_prog.data(), prog->n_outputs, d_arena, d_offs, d_lens, n,
+                              reinterpret_cast<const uint32_t*>(d_values), values_stride, d_text, text_stride,
+                              d_out_text, out_stride, reinterpret_cast<uint32_t*>(d_out), s));
     return AUTHJX_OK;
 }
 
@@ -103,27 +76,27 @@ int authjx_render_batch(authjx_ctx* ctx, const authjx_render* prog, const uint8_
     if (values_stride < prog->n_slots || out_stride == 0 || out_stride % 16u != 0) return AUTHJX_EINVAL;
     if (n == 0) return AUTHJX_OK;
     if (!arena || !offs || !lens || !out_text || !out || (prog->n_slots && !values)) return AUTHJX_EINVAL;
-    for (uint32_t r = 0; r < n; r++)
-        if (offs[r] + lens[r] > arena_len) return AUTHJX_EINVAL;
+    if (!ajx::spans_in_arena(offs, lens, n, arena_len)) return AUTHJX_EINVAL;
     const size_t val_bytes = (size_t)n * values_stride * sizeof(authjx_value);
     const size_t text_bytes = text ? (size_t)n * text_stride : 0;
     const size_t outt_bytes = (size_t)n * out_stride, out_bytes = (size_t)n * prog->n_outputs * sizeof(authjx_rendered);
-    const size_t o_offs = up256(arena_len), o_lens = up256(o_offs + (size_t)n * 8);
-    const size_t o_val = up256(o_lens + (size_t)n * 4), o_text = up256(o_val + val_bytes);
-    const size_t o_outt = up256(o_text + text_bytes), o_out = up256(o_outt + outt_bytes);
-    const size_t total = up256(o_out + out_bytes) + 256;
-    RENDER_HIP_OK(hipSetDevice(prog->device));
-    DeviceBuf buf;
-    RENDER_HIP_OK(hipMalloc(&buf.p, total));
-    uint8_t* b = buf.p;
-    hipStream_t s = ajx_ctx_stream(ctx);
-    if (arena_len) RENDER_HIP_OK(hipMemcpyAsync(b, arena, arena_len, hipMemcpyHostToDevice, s));
-    RENDER_HIP_OK(hipMemcpyAsync(b + o_offs, offs, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    RENDER_HIP_OK(hipMemcpyAsync(b + o_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (val_bytes) RENDER_HIP_OK(hipMemcpyAsync(b + o_val, values, val_bytes, hipMemcpyHostToDevice, s));
-    if (text_bytes) RENDER_HIP_OK(hipMemcpyAsync(b + o_text, text, text_bytes, hipMemcpyHostToDevice, s));
+    ajx::StageLayout lay;
+    lay.add(arena_len);  // (the arena at 0)
+    const size_t o_offs = lay.add((size_t)n * 8), o_lens = lay.add((size_t)n * 4);
+    const size_t o_val = lay.add(val_bytes), o_text = lay.add(text_bytes);
+    const size_t o_outt = lay.add(outt_bytes), o_out = lay.add(out_bytes);
+    HIP_OK(hipSetDevice(prog->device));
+    ajx::DeviceBuf buf;  // (a buffer per call: freed on every return)
+    HIP_OK(buf.reserve(lay.total() + 256));
+    uint8_t* b = buf.data();
+    hipStream_t s = ctx->stream;
+    if (arena_len) HIP_OK(hipMemcpyAsync(b, arena, arena_len, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(b + o_offs, offs, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(b + o_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (val_bytes) HIP_OK(hipMemcpyAsync(b + o_val, values, val_bytes, hipMemcpyHostToDevice, s));
+    if (text_bytes) HIP_OK(hipMemcpyAsync(b + o_text, text, text_bytes, hipMemcpyHostToDevice, s));
     // (the slots' unspecified bytes come back as the caller's own: the host copy keeps them)
-    RENDER_HIP_OK(hipMemcpyAsync(b + o_outt, out_text, outt_bytes, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(b + o_outt, out_text, outt_bytes, hipMemcpyHostToDevice, s));
     const int rc = authjx_render_batch_device(
         ctx, prog, b, (const uint64_t*)(b + o_offs), (const uint32_t*)(b + o_lens), n,
         (const authjx_value*)(b + o_val), values_stride, text ? b + o_text : nullptr, text_stride, b + o_outt,
@@ -132,8 +105,8 @@ int authjx_render_batch(authjx_ctx* ctx, const authjx_render* prog, const uint8_
         (void)hipStreamSynchronize(s);
         return rc;
     }
-    RENDER_HIP_OK(hipMemcpyAsync(out_text, b + o_outt, outt_bytes, hipMemcpyDeviceToHost, s));
-    if (out_bytes) RENDER_HIP_OK(hipMemcpyAsync(out, b + o_out, out_bytes, hipMemcpyDeviceToHost, s));
-    RENDER_HIP_OK(hipStreamSynchronize(s));
+    HIP_OK(hipMemcpyAsync(out_text, b + o_outt, outt_bytes, hipMemcpyDeviceToHost, s));
+    if (out_bytes) HIP_OK(hipMemcpyAsync(out, b + o_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
     return AUTHJX_OK;
 }

@@ -1,4 +1,4 @@
-"""GPU: the micro-batcher's serving path (ajx_api.cpp authjx_batcher::evaluate): one staging
+"""GPU: the micro-batcher's serving path (ajx_batcher_api.cpp authjx_batcher::evaluate): one staging
 copy per batch (documents, offsets, lengths, ruleset indices, blob pointers), results
 written by the kernel into mapped pinned memory, and the streaming kernel's counters left
 zero by its last wave. Batches of many rulesets, invalid and mutated documents (the exact

@@ -66,3 +66,18 @@ def test_workspace_lifetime_under_tsan():
                        env=env)
     assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
     assert r.stdout.startswith("ok ") and "errors 0" in r.stdout
+
+
+def test_buffer_ownership_under_asan_ubsan():
+    """The C-ABI's owned buffers and staged copies (ajx_api.cpp, ajx_batcher_api.cpp,
+    ajx_hostbuf.h) on the same stand-in, sequentially (tests/native/api_host.cpp): batches of
+    3, 64, 65, 4097 and 130 requests through every device and host-buffer entry point on one
+    context and stream, 65 rulesets in one batch, spans past the arena or wrapping 2^64 and
+    stale capture rows refused, one batcher destroyed by hand and one by authjx_shutdown —
+    under ASan + UBSan with leak detection (the stand-in's allocations are exact-size)."""
+    subprocess.run(["make", "-s", "-C", _NATIVE, "api_host"], check=True, timeout=600)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([os.path.join(_NATIVE, "api_host")], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stdout.startswith("ok ") and "FAIL" not in r.stdout
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
