@@ -48,6 +48,7 @@ struct Workspace {
     hipEvent_t sets_ev[2] = {nullptr, nullptr};
     bool sets_ev_rec[2] = {false, false};
     std::vector<const uint8_t*> last_sets;
+    ajx::PtrTable progs;  // the render programs of a multi-program batch (with_ptr_table)
     // [0] = count, [1..] = ids: requests for the exact scan (the streaming kernel: its
     // ajx::StreamCounters, the ids after them)
     ajx::DeviceBuf slow;
@@ -106,8 +107,10 @@ void destroy_workspace(Workspace* w) {
                 break;
             }
     }
-    for (int k = 0; k < 2; k++)
+    for (int k = 0; k < 2; k++) {
         if (w->sets_ev[k]) (void)hipEventDestroy(w->sets_ev[k]);
+        if (w->progs.ev[k]) (void)hipEventDestroy(w->progs.ev[k]);
+    }
     if (w->ev0) (void)hipEventDestroy(w->ev0);
     delete w;  // (its buffers; ev1 goes with the last holder of w->end)
 }
@@ -362,6 +365,43 @@ void retire_stream(authjx_ctx* ctx, hipStream_t s) {
             }
     }
     if (dead) destroy_workspace(w);  // (else the call still on that stream does, when it ends)
+}
+
+int with_ptr_table(authjx_ctx* ctx, void* stream, const uint8_t* const* ptrs, uint32_t n,
+                   const std::function<hipError_t(const uint8_t* const*, hipStream_t)>& launch) {
+    WsLock wl(ctx, stream);
+    Workspace* w = wl.w;
+    if (!w) return AUTHJX_EDEVICE;
+    HIP_OK(hipSetDevice(ctx->device));
+    ajx::PtrTable& t = w->progs;
+    if (t.last.empty() || !std::equal(t.last.begin(), t.last.end(), ptrs, ptrs + n)) {
+        if (n > t.cap) {  // (grows once the stream's earlier batches are done with the old table)
+            const uint32_t cap = n < 64 ? 64 : n;
+            t.cap = 0;
+            t.last.clear();
+            t.rec[0] = t.rec[1] = false;
+            HIP_OK(t.dev.reserve(2 * (size_t)cap * sizeof(uint8_t*), w->stream));
+            HIP_OK(t.host.reserve(2 * (size_t)cap * sizeof(uint8_t*), w->stream));
+            for (int k = 0; k < 2; k++)
+                if (!t.ev[k]) HIP_OK(hipEventCreateWithFlags(&t.ev[k], hipEventDisableTiming));
+            t.cap = cap;
+        }
+        // the other slot: free once the last batch that read it has finished
+        const uint32_t k = t.last.empty() ? 0u : 1u - t.slot;
+        if (t.rec[k]) HIP_OK(hipEventSynchronize(t.ev[k]));
+        const uint8_t** h = t.host.as<const uint8_t*>() + (size_t)k * t.cap;
+        std::memcpy(h, ptrs, n * sizeof(uint8_t*));
+        HIP_OK(hipMemcpyAsync(t.dev.as<const uint8_t*>() + (size_t)k * t.cap, h, n * sizeof(uint8_t*),
+                              hipMemcpyHostToDevice, w->stream));
+        t.slot = k;
+        t.last.assign(ptrs, ptrs + n);
+    }
+    HIP_OK(launch(t.dev.as<const uint8_t*>() + (size_t)t.slot * t.cap, w->stream));
+    HIP_OK(hipEventRecord(t.ev[t.slot], w->stream));
+    t.rec[t.slot] = true;
+    HIP_OK(hipEventRecord(w->ev1, w->stream));  // (retiring the stream waits for this batch)
+    w->ran = true;
+    return AUTHJX_OK;
 }
 
 int eval_device(authjx_ctx* ctx, const authjx_ruleset* const* sets, uint32_t n_sets, const uint32_t* d_set_of_req,

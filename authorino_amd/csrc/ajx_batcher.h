@@ -44,6 +44,8 @@ constexpr int kBatchOk = 0;
 constexpr int kBatchTimedOut = -5;  // AUTHJX_ETIMEDOUT
 constexpr int kBatchClosed = -6;    // AUTHJX_ECLOSED
 
+struct PhaseFacts;  // ajx_phase.h
+
 struct BatchReq {
     const void* rs = nullptr;  // the ruleset (opaque to the core)
     uint32_t n_out = 1;        // results per request (the ruleset's trees)
@@ -53,6 +55,11 @@ struct BatchReq {
     uint64_t enq_ns = 0;
     uint8_t* out_tri = nullptr;  // n_out entries
     int32_t* out_err = nullptr;  // n_out entries or null
+    // a phase request (ajx_phase.h; opaque to the core): its response outputs go to
+    // out_text (the phase's out_stride bytes) and out_rec (its program's records)
+    const PhaseFacts* phase = nullptr;
+    uint8_t* out_text = nullptr;
+    void* out_rec = nullptr;
     // completion. Wake mode 0: this request's condition variable; 1: `flag`, then one
     // broadcast on the core's completion word for the whole batch; 2: `flag` as this
     // request's own futex word; 3: as 2, woken as node `idx` of a binary tree over the batch

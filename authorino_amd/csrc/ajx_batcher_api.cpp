@@ -1,11 +1,15 @@
 // ajx_batcher_api.cpp — the micro-batcher's entry points of the C-ABI (include/authjx.h):
-// ajx_batcher.h's queue with the device evaluation (eval_device, ajx_api.cpp) plugged in.
+// ajx_batcher.h's queue with the device evaluation (eval_device, ajx_api.cpp) plugged in,
+// and behind it, for the batch's phase requests (ajx_phase.h), the select and the render of
+// their AuthConfigs' response outputs on the same stream.
 #include <atomic>
 #include <cstring>
 #include <thread>
 
 #include "ajx_host.h"
 #include "ajx_batcher.h"
+#include "ajx_phase.h"
+#include "ajx_phase_api.h"
 
 namespace {
 
@@ -30,8 +34,12 @@ struct authjx_batcher {
     // without a synchronize (the worker has waited for its last batch)
     struct Lane {
         hipStream_t stream = nullptr;
-        ajx::PinnedBuf pinned;  // arena | offs | lens | set_of_req | sets | outputs (written by the kernel)
+        // arena | offs | lens | set_of_req | sets | the phase subset's offs, lens, program
+        // indices, program table and per-group ruleset indices | outputs (written by the
+        // kernels): tri, err, the phase requests' records and output slots
+        ajx::PinnedBuf pinned;
         ajx::DeviceBuf dev;     // the inputs' copy with zero-copy off
+        ajx::DeviceBuf mid;     // the phase subset's values and text slots (select -> render)
     } lanes[kBatcherMaxWorkers];
     uint32_t n_lanes = 2;
     uint32_t sync_mode = 0, zcopy = 0;
@@ -61,11 +69,27 @@ struct authjx_batcher {
         lay.add(arena_len + 1);  // (the documents, at 0, and a terminating NUL)
         const size_t o_offs = lay.add((size_t)n * 8), o_lens = lay.add((size_t)n * 4);
         const size_t o_sor = lay.add((size_t)n * 4), o_sets = lay.add(sets.size() * sizeof(uint8_t*));
+        // the phase requests: further inputs (nothing for a batch without any), outputs,
+        // and the values and text slots between the select and the render in device memory
+        const ajx::PhasePlan plan = ajx::plan_phases(reqs);
+        const uint32_t m = plan.n(), vs = plan.values_stride, rs = plan.records_stride;
+        const size_t o_poffs = lay.add((size_t)m * 8), o_plens = lay.add((size_t)m * 4);
+        const size_t o_por = lay.add((size_t)m * 4), o_ptab = lay.add(plan.progs.size() * sizeof(uint8_t*));
+        const size_t o_psor = lay.add((size_t)m * 4);
         const size_t in_bytes = lay.total();  // (the outputs after it: host side only)
         const size_t o_tri = lay.add((size_t)n * nt), o_err = lay.add((size_t)n * nt * 4);
+        const size_t o_rec = lay.add((size_t)m * rs * 12);
+        ajx::StageLayout mid;
+        const size_t o_val = mid.add((size_t)m * vs * 12);
+        std::vector<size_t> o_text(plan.groups.size()), o_out(plan.groups.size());
+        for (size_t g = 0; g < plan.groups.size(); g++) {
+            o_text[g] = mid.add((size_t)plan.groups[g].count * plan.groups[g].text_stride);
+            o_out[g] = lay.add((size_t)plan.groups[g].count * plan.groups[g].out_stride);
+        }
         HIP_OK(hipSetDevice(ctx->device));
         HIP_OK(L.pinned.reserve(lay.total()));
         HIP_OK(L.dev.reserve(in_bytes));
+        HIP_OK(L.mid.reserve(mid.total()));
         uint8_t* const h = L.pinned.data();
         const uint64_t t0 = ajx::mono_ns();
         uint64_t* offs = (uint64_t*)(h + o_offs);
@@ -81,6 +105,19 @@ struct authjx_batcher {
         std::memcpy(h + o_sor, sor.data(), (size_t)n * 4);
         const uint8_t** hs = (const uint8_t**)(h + o_sets);
         for (size_t k = 0; k < sets.size(); k++) hs[k] = sets[k] ? sets[k]->d_blob.data() : nullptr;
+        if (m) {  // (the phase subset reads the same staged documents)
+            uint64_t* poffs = (uint64_t*)(h + o_poffs);
+            uint32_t* plens = (uint32_t*)(h + o_plens);
+            for (uint32_t j = 0; j < m; j++) {
+                poffs[j] = offs[plan.req[j]];
+                plens[j] = lens[plan.req[j]];
+            }
+            std::memcpy(h + o_por, plan.prog_of.data(), (size_t)m * 4);
+            const uint8_t** pt = (const uint8_t**)(h + o_ptab);
+            for (size_t k = 0; k < plan.progs.size(); k++) pt[k] = (const uint8_t*)plan.progs[k];
+            for (const ajx::PhaseGroup& g : plan.groups)
+                std::memcpy(h + o_psor + (size_t)g.first * 4, g.set_of.data(), (size_t)g.count * 4);
+        }
         const uint64_t t1 = ajx::mono_ns();
         // (zero-copy: the kernel reads the batch from the mapped staging buffer over PCIe)
         const uint8_t* in = zcopy ? L.pinned.device() : L.dev.data();
@@ -90,6 +127,30 @@ struct authjx_batcher {
                                    L.pinned.device() + o_tri, (int32_t*)(L.pinned.device() + o_err), nullptr, 0,
                                    L.stream, (const uint8_t* const*)(in + o_sets));
         if (rc != AUTHJX_OK) return rc;
+        // the phase requests' values (the multi-set select over their selector rulesets as
+        // runs) and outputs (the multi-program render), one pair of launches per group
+        uint8_t* const out_dev = L.pinned.device();
+        for (size_t gi = 0; gi < plan.groups.size(); gi++) {
+            const ajx::PhaseGroup& g = plan.groups[gi];
+            const uint64_t* d_offs = (const uint64_t*)(in + o_poffs) + g.first;
+            const uint32_t* d_lens = (const uint32_t*)(in + o_plens) + g.first;
+            authjx_value* d_val = (authjx_value*)(L.mid.data() + o_val) + (size_t)g.first * vs;
+            uint8_t* d_text = g.text_stride ? L.mid.data() + o_text[gi] : nullptr;
+            const int rc2 = authjx_select_text_batch_device(
+                ctx, (const authjx_ruleset* const*)g.sets.data(), (uint32_t)g.sets.size(),
+                (const uint32_t*)(in + o_psor) + g.first, in, d_offs, d_lens, g.count, d_val, vs, d_text,
+                g.text_stride, L.stream);
+            if (rc2 != AUTHJX_OK) {
+                (void)hipStreamSynchronize(L.stream);  // (the evaluation queued above reads the lane's buffers)
+                return rc2;
+            }
+            const ajx::PhaseRender render = reqs[plan.req[g.first]]->phase->render;
+            HIP_OK((hipError_t)render((const uint8_t* const*)(in + o_ptab), (uint32_t)plan.progs.size(),
+                                      (const uint32_t*)(in + o_por) + g.first, in, d_offs, d_lens, g.count,
+                                      (const uint32_t*)d_val, vs, d_text, g.text_stride, out_dev + o_out[gi],
+                                      g.out_stride, (uint32_t*)(out_dev + o_rec) + (size_t)g.first * rs * 3, rs,
+                                      L.stream));
+        }
         const uint64_t t2 = ajx::mono_ns();
         if (sync_mode == 1) {
             for (;;) {
@@ -111,6 +172,12 @@ struct authjx_batcher {
                 reqs[i]->out_tri[k] = tri[(size_t)i * nt + k];
                 if (reqs[i]->out_err) reqs[i]->out_err[k] = err[(size_t)i * nt + k];
             }
+        }
+        for (size_t gi = 0; gi < plan.groups.size(); gi++) {
+            const ajx::PhaseGroup& g = plan.groups[gi];
+            for (uint32_t j = 0; j < g.count; j++)
+                ajx::deliver_phase(*reqs[plan.req[g.first + j]], h + o_out[gi] + (size_t)j * g.out_stride,
+                                   (const uint32_t*)(h + o_rec) + (size_t)(g.first + j) * rs * 3);
         }
         return AUTHJX_OK;
     }
@@ -209,6 +276,76 @@ int authjx_batcher_eval(authjx_batcher* b, const authjx_ruleset* rs, const uint8
     r.out_tri = out_tristate;
     r.out_err = out_err_idx;
     return b->core->submit(r);
+}
+
+int authjx_batcher_phase(authjx_batcher* b, const authjx_phase* ph, const uint8_t* doc, size_t len,
+                         uint64_t timeout_us, uint8_t* out_tristate, int32_t* out_err_idx, uint8_t* out_text,
+                         authjx_rendered* out) {
+    if (!b || !ph || (!doc && len) || !out_tristate || len >= (1ull << 32)) return AUTHJX_EINVAL;
+    if (!out_text || (ph->f.n_outputs && !out) || ph->device != b->ctx->device || !ph->f.render)
+        return AUTHJX_EINVAL;
+    ajx::BatchReq r;
+    r.rs = ph->rules;
+    r.n_out = ph->rules->c.n_trees;
+    r.doc = doc;
+    r.len = len;
+    r.deadline_ns = timeout_us ? ajx::mono_ns() + timeout_us * 1000ull : 0;
+    r.out_tri = out_tristate;
+    r.out_err = out_err_idx;
+    r.phase = &ph->f;
+    r.out_text = out_text;
+    r.out_rec = out;
+    return b->core->submit(r);
+}
+
+// Profiling only (not in authjx.h): authjx_debug_loadgen for phase requests. Thread t
+// submits requests i = t, t + threads, ... as authjx_batcher_phase(phases[por[i]], ...);
+// lat_ns[i] = that call's latency, out_tri[i] its first result, out_hash[i] the 64-bit
+// FNV-1a of its rendered outputs (each output's status byte, then its bytes when rendered).
+int authjx_debug_phase_loadgen(authjx_batcher* b, const authjx_phase* const* phases, const uint32_t* por,
+                               const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                               uint32_t threads, uint64_t* lat_ns, uint8_t* out_tri, uint64_t* out_hash,
+                               uint64_t* wall_ns) {
+    if (!b || !phases || !por || !arena || !offs || !lens || !lat_ns || !out_tri || !out_hash || !wall_ns ||
+        threads == 0)
+        return AUTHJX_EINVAL;
+    std::atomic<int> first_rc{AUTHJX_OK};
+    const uint64_t t0 = ajx::mono_ns();
+    std::vector<std::thread> ts;
+    for (uint32_t t = 0; t < threads; t++)
+        ts.emplace_back([&, t] {
+            uint8_t tri[64];
+            std::vector<uint8_t> text;
+            std::vector<authjx_rendered> rec;
+            for (uint32_t i = t; i < n; i += threads) {
+                const authjx_phase* ph = phases[por[i]];
+                if (!ph || ph->rules->c.n_trees > 64) {
+                    first_rc.store(AUTHJX_EINVAL);
+                    return;
+                }
+                text.resize(ph->f.out_stride);
+                rec.resize(ph->f.n_outputs + 1);
+                const uint64_t a = ajx::mono_ns();
+                const int rc = authjx_batcher_phase(b, ph, arena + offs[i], lens[i], 0, tri, nullptr, text.data(),
+                                                    rec.data());
+                lat_ns[i] = ajx::mono_ns() - a;
+                out_tri[i] = tri[0];
+                uint64_t hsh = 0xcbf29ce484222325ull;
+                for (uint32_t k = 0; rc == AUTHJX_OK && k < ph->f.n_outputs; k++) {
+                    hsh = (hsh ^ rec[k].status) * 0x100000001b3ull;
+                    for (uint32_t q = 0; rec[k].status == AUTHJX_RENDER_OK && q < rec[k].len; q++)
+                        hsh = (hsh ^ text[rec[k].start + q]) * 0x100000001b3ull;
+                }
+                out_hash[i] = hsh;
+                if (rc != AUTHJX_OK) {
+                    int ok = AUTHJX_OK;
+                    first_rc.compare_exchange_strong(ok, rc);
+                }
+            }
+        });
+    for (auto& th : ts) th.join();
+    *wall_ns = ajx::mono_ns() - t0;
+    return first_rc.load();
 }
 
 // Profiling only (not in authjx.h): the serving path under load. `threads` producer threads

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -80,6 +81,12 @@ int eval_device(authjx_ctx* ctx, const authjx_ruleset* const* sets, uint32_t n_s
                 uint8_t* d_out_tristate, int32_t* d_out_err_idx, uint64_t* d_out_bitmap, uint32_t bitmap_stride_words,
                 void* stream, const uint8_t* const* d_sets_pre);
 
+// Queues launch(table, s) on `stream` (NULL: the context's), `table` being ptrs[0, n), n > 0,
+// as a device table of that stream's workspace, uploaded on the stream when it differs from
+// the last call's. AUTHJX_EDEVICE when an upload or the launch fails.
+int with_ptr_table(authjx_ctx* ctx, void* stream, const uint8_t* const* ptrs, uint32_t n,
+                   const std::function<hipError_t(const uint8_t* const*, hipStream_t)>& launch);
+
 // retires the workspace of stream s (the caller holds no lock)
 void retire_stream(authjx_ctx* ctx, hipStream_t s);
 
@@ -95,6 +102,19 @@ struct StageLayout {
         return at;
     }
     size_t total() const { return end; }
+};
+
+// A table of device pointers that kernels index, kept per stream: two slots (device + pinned
+// source each), so a call with another list fills the slot the call before the last one
+// used; that call's event, not a stream synchronize, guards the reuse.
+struct PtrTable {
+    DeviceBuf dev;
+    PinnedBuf host;
+    uint32_t cap = 0;  // entries per slot
+    uint32_t slot = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool rec[2] = {false, false};
+    std::vector<const uint8_t*> last;  // the current slot's entries (empty: none uploaded)
 };
 
 // every request's span lies in the arena (written so that offs + lens cannot wrap)

@@ -489,4 +489,23 @@ AJX_HD void render_request(const uint8_t* prog, const uint8_t* doc, uint32_t doc
     w.flush();
 }
 
+// prog_of_req entry of a request that renders nothing (AUTHJX_RENDER_NO_PROGRAM)
+constexpr uint32_t kRenderNoProgram = 0xFFFFFFFFu;
+
+// A request of a multi-program batch: renders progs[prog], its other arguments as
+// render_request's (res: room for that program's n_outputs records). prog ==
+// kRenderNoProgram, or any index that is not below n_progs: nothing is read and nothing
+// written, neither the output slot nor the records.
+// On the device every lane holds its own program pointer, and the program's header, op and
+// literal reads are vector loads where the one-program kernel has scalar ones. In a wave of
+// one program (the common case: batches are ordered by ruleset) all lanes of such a load read
+// one address; lanes of different programs run together, not in turns (DESIGN §5.15 has the
+// build report and the waterfall that was tried instead).
+AJX_HD void render_request_multi(const uint8_t* const* progs, uint32_t n_progs, uint32_t prog, const uint8_t* doc,
+                                 uint32_t doc_len, const uint32_t* vals, const uint8_t* text, uint32_t text_cap,
+                                 uint8_t* out, uint32_t out_cap, uint32_t* res, const RenderStack& st) {
+    if (prog >= n_progs) return;
+    render_request(progs[prog], doc, doc_len, vals, text, text_cap, out, out_cap, res, st);
+}
+
 }  // namespace ajx

@@ -28,6 +28,37 @@ __global__ __launch_bounds__(256) void ajx_render_values(const uint8_t* __restri
                    out_stride, out + (size_t)r * n_outputs * 3u, st);
 }
 
+// The multi-program instance: request r renders progs[prog_of_req[r]] (prog_of_req nullptr:
+// progs[0]) and writes that program's records at out[r * records_stride ...]. A kernel of
+// its own: the one above keeps its program pointer as a kernel argument and its code.
+__global__ __launch_bounds__(256) void ajx_render_values_multi(
+    const uint8_t* const* __restrict__ progs, uint32_t n_progs, const uint32_t* __restrict__ prog_of_req,
+    const uint8_t* __restrict__ arena, const uint64_t* __restrict__ offs, const uint32_t* __restrict__ lens, uint32_t n,
+    const uint32_t* __restrict__ values, uint32_t values_stride, const uint8_t* __restrict__ text, uint32_t text_stride,
+    uint8_t* __restrict__ out_text, uint32_t out_stride, uint32_t* __restrict__ out, uint32_t records_stride) {
+    __shared__ uint32_t levels[kMaxRenderDepth * kRenderLevelWords * kRenderBlock];
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const RenderStack st{levels + threadIdx.x, kRenderBlock};
+    render_request_multi(progs, n_progs, prog_of_req ? prog_of_req[r] : 0u, arena + offs[r], lens[r],
+                         values + (size_t)r * values_stride * 3u, text ? text + (size_t)r * text_stride : nullptr,
+                         text_stride, out_text + (size_t)r * out_stride, out_stride,
+                         out + (size_t)r * records_stride * 3u, st);
+}
+
+hipError_t launch_render_multi(const uint8_t* const* d_progs, uint32_t n_progs, const uint32_t* prog_of_req,
+                               const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                               const uint32_t* values, uint32_t values_stride, const uint8_t* text,
+                               uint32_t text_stride, uint8_t* out_text, uint32_t out_stride, uint32_t* out,
+                               uint32_t records_stride, hipStream_t stream) {
+    if (n == 0 || n_progs == 0) return hipSuccess;
+    const uint32_t grid = (n + kRenderBlock - 1) / kRenderBlock;
+    hipLaunchKernelGGL(ajx_render_values_multi, dim3(grid), dim3(kRenderBlock), 0, stream, d_progs, n_progs,
+                       prog_of_req, arena, offs, lens, n, values, values_stride, text, text_stride, out_text,
+                       out_stride, out, records_stride);
+    return hipGetLastError();
+}
+
 hipError_t launch_render(const uint8_t* d_prog, uint32_t n_outputs, const uint8_t* arena, const uint64_t* offs,
                          const uint32_t* lens, uint32_t n, const uint32_t* values, uint32_t values_stride,
                          const uint8_t* text, uint32_t text_stride, uint8_t* out_text, uint32_t out_stride,

@@ -8,12 +8,6 @@
 #include "ajx_render_api.h"
 #include "ajx_render_prog.h"
 
-struct authjx_render {
-    int device = 0;
-    ajx::DeviceBuf d_prog;
-    uint32_t n_outputs = 0, n_slots = 0;
-};
-
 static_assert(sizeof(authjx_rendered) == 12, "authjx_rendered is three u32 words on the device");
 
 int authjx_render_compile(authjx_ctx* ctx, const authjx_render_output* outs, uint32_t n_outputs, uint32_t n_slots,
@@ -66,6 +60,35 @@ int authjx_render_batch_device(authjx_ctx* ctx, const authjx_render* prog, const
                               reinterpret_cast<const uint32_t*>(d_values), values_stride, d_text, text_stride,
                               d_out_text, out_stride, reinterpret_cast<uint32_t*>(d_out), s));
     return AUTHJX_OK;
+}
+
+int authjx_render_batch_multi_device(authjx_ctx* ctx, const authjx_render* const* progs, uint32_t n_progs,
+                                     const uint32_t* d_prog_of_req, const uint8_t* d_arena, const uint64_t* d_offs,
+                                     const uint32_t* d_lens, uint32_t n, const authjx_value* d_values,
+                                     uint32_t values_stride, const uint8_t* d_text, uint32_t text_stride,
+                                     uint8_t* d_out_text, uint32_t out_stride, authjx_rendered* d_out,
+                                     uint32_t records_stride, void* stream) {
+    if (!ctx || !progs || n_progs == 0) return AUTHJX_EINVAL;
+    if (out_stride == 0 || out_stride % 16u != 0 || (n_progs > 1 && !d_prog_of_req)) return AUTHJX_EINVAL;
+    std::vector<const uint8_t*> blobs(n_progs);
+    uint32_t slots = 0;
+    for (uint32_t i = 0; i < n_progs; i++) {
+        const authjx_render* p = progs[i];
+        if (!p || p->device != ctx->device || values_stride < p->n_slots || records_stride < p->n_outputs)
+            return AUTHJX_EINVAL;
+        blobs[i] = p->d_prog.data();
+        slots = std::max(slots, p->n_slots);
+    }
+    if (n && (!d_arena || !d_offs || !d_lens || !d_out_text || !d_out || (slots && !d_values)))
+        return AUTHJX_EINVAL;
+    if (((uintptr_t)d_out_text & 15u) != 0) return AUTHJX_EINVAL;
+    if (n == 0) return AUTHJX_OK;
+    return with_ptr_table(ctx, stream, blobs.data(), n_progs, [&](const uint8_t* const* d_progs, hipStream_t s) {
+        return ajx::launch_render_multi(d_progs, n_progs, d_prog_of_req, d_arena, d_offs, d_lens, n,
+                                        reinterpret_cast<const uint32_t*>(d_values), values_stride, d_text,
+                                        text_stride, d_out_text, out_stride, reinterpret_cast<uint32_t*>(d_out),
+                                        records_stride, s);
+    });
 }
 
 int authjx_render_batch(authjx_ctx* ctx, const authjx_render* prog, const uint8_t* arena, uint64_t arena_len,

@@ -5,6 +5,14 @@
 #include <stdint.h>
 
 #include "../../include/authjx.h"
+#include "ajx_hostbuf.h"
+
+// a render program resident in device memory (authjx_render_compile)
+struct authjx_render {
+    int device = 0;
+    ajx::DeviceBuf d_prog;
+    uint32_t n_outputs = 0, n_slots = 0;
+};
 
 // the context's device and its own stream (ajx_api.cpp)
 int ajx_ctx_device(const authjx_ctx* ctx);
@@ -20,5 +28,15 @@ hipError_t launch_render(const uint8_t* d_prog, uint32_t n_outputs, const uint8_
                          const uint32_t* lens, uint32_t n, const uint32_t* values, uint32_t values_stride,
                          const uint8_t* text, uint32_t text_stride, uint8_t* out_text, uint32_t out_stride,
                          uint32_t* out, hipStream_t stream);
+
+// The same kernel's multi-program instance: request r renders d_progs[prog_of_req[r]]
+// (prog_of_req nullptr: d_progs[0]) and writes that program's records at
+// out[r * records_stride ...]; an entry that is not below n_progs (0xFFFFFFFF: "no program")
+// reads and writes nothing. d_progs: a device table of n_progs program blobs.
+hipError_t launch_render_multi(const uint8_t* const* d_progs, uint32_t n_progs, const uint32_t* prog_of_req,
+                               const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                               const uint32_t* values, uint32_t values_stride, const uint8_t* text,
+                               uint32_t text_stride, uint8_t* out_text, uint32_t out_stride, uint32_t* out,
+                               uint32_t records_stride, hipStream_t stream);
 
 }  // namespace ajx

@@ -654,6 +654,18 @@ class ResponseSelectors(ValueSelectors):
                            for s, ln, st in rec[r]])
         return values, rec[:, :, 2]
 
+    def phase(self, rules, text_stride: Optional[int] = None, out_stride: Optional[int] = None):
+        """These response configs behind the micro-batcher (runtime.Batcher.phase): the
+        selector ruleset and the render program above as a runtime.Phase of the AuthConfig
+        whose rules are `rules`, and the header key of each of its outputs."""
+        from .runtime import Phase
+
+        prog, _ = self._render_program()
+        keys = [c.wrapper_key for c in self.configs if c.wrapper == HTTP_HEADER_WRAPPER]
+        ph = Phase(self.ctx, rules, self.ruleset, prog, self.TEXT_STRIDE if text_stride is None else text_stride,
+                   self.RENDER_STRIDE if out_stride is None else out_stride)
+        return ph, keys
+
 
 # authjx_render_op.op / authjx_rendered.status (include/authjx.h AUTHJX_R_*, AUTHJX_RENDER_*)
 R_LIT, R_STRING, R_STRING_ESC, R_SPRINT, R_MARSHAL = range(5)

@@ -53,6 +53,7 @@ class _RenderOutput(C.Structure):
 # authjx_render_op.op (AUTHJX_R_*) and authjx_rendered.status (AUTHJX_RENDER_*)
 R_LIT, R_STRING, R_STRING_ESC, R_SPRINT, R_MARSHAL = range(5)
 RENDER_OK, RENDER_UNRENDERED = 0, 1
+RENDER_NO_PROGRAM = 0xFFFFFFFF  # a prog_of_req entry (AUTHJX_RENDER_NO_PROGRAM)
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -69,7 +70,8 @@ EXPORTS = [
     "authjx_index_new", "authjx_index_free", "authjx_index_set", "authjx_index_delete_key", "authjx_index_get",
     "authjx_index_lookup_batch", "authjx_pack_json", "authjx_build_hash",
     "authjx_render_compile", "authjx_render_free", "authjx_render_outputs", "authjx_render_batch_device",
-    "authjx_render_batch",
+    "authjx_render_batch", "authjx_render_batch_multi_device",
+    "authjx_phase_create", "authjx_phase_free", "authjx_phase_outputs", "authjx_batcher_phase",
 ]
 
 
@@ -206,6 +208,22 @@ def load_library(path: str = LIB_PATH):
                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                 C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
             L.authjx_render_batch.restype = C.c_int
+        if os.environ.get("AUTHJX_LIB") is None or hasattr(L, "authjx_render_batch_multi_device"):
+            L.authjx_render_batch_multi_device.argtypes = [
+                C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                C.c_uint32, C.c_void_p]
+            L.authjx_render_batch_multi_device.restype = C.c_int
+            L.authjx_phase_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_void_p)]
+            L.authjx_phase_create.restype = C.c_int
+            L.authjx_phase_free.argtypes = [C.c_void_p]
+            L.authjx_phase_free.restype = None
+            L.authjx_phase_outputs.argtypes = [C.c_void_p]
+            L.authjx_phase_outputs.restype = C.c_uint32
+            L.authjx_batcher_phase.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64,
+                                               C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
+            L.authjx_batcher_phase.restype = C.c_int
         L.authjx_debug_last_error.argtypes = []
         L.authjx_debug_last_error.restype = C.c_char_p
         _lib = L
@@ -437,6 +455,22 @@ class Context:
             C.c_void_p(stream) if stream else None)
         _check(rc, "authjx_render_batch_device")
 
+    def render_multi_device(self, progs, prog_of_req, arena, offs, lens, values, out_text, out, text=None,
+                            stream=None) -> None:
+        """authjx_render_batch_multi_device on HBM-resident torch tensors: request r renders
+        progs[prog_of_req[r]] (u32[n], or None with one program; RENDER_NO_PROGRAM: the request
+        is left alone). values u32[n][values_stride][3], out u32[n][records_stride][3], the
+        rest as render_device. A None among progs stands for a NULL program (EINVAL).
+        Asynchronous."""
+        n = int(lens.numel())
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        parr = (C.c_void_p * max(len(progs), 1))(*[p._h.value if p is not None else None for p in progs])
+        rc = load_library().authjx_render_batch_multi_device(
+            self._h, parr, len(progs), ptr(prog_of_req), ptr(arena), ptr(offs), ptr(lens), n, ptr(values),
+            int(values.shape[1]), ptr(text), int(text.shape[1]) if text is not None else 0, ptr(out_text),
+            int(out_text.shape[1]), ptr(out), int(out.shape[1]), C.c_void_p(stream) if stream else None)
+        _check(rc, "authjx_render_batch_multi_device")
+
     def render_host_arena(self, prog: "RenderProgram", arena, offs, lens, values, text=None, out_stride: int = 4096,
                           out_text=None):
         """authjx_render_batch: (u32[n][n_outputs][3] records {start, len, status}, u8[n][out_stride]
@@ -578,6 +612,32 @@ class RenderProgram:
             self._h = None
 
 
+class Phase:
+    """One AuthConfig as the serving path sees it (authjx_phase_create): its rules, the
+    selector ruleset of its response values and the render program over them. The three are
+    borrowed: this object keeps them alive."""
+
+    def __init__(self, ctx: Context, rules: "Ruleset", selectors: "Ruleset", prog: "RenderProgram",
+                 text_stride: int = 4096, out_stride: int = 1024):
+        h = C.c_void_p()
+        ptr = lambda o: o._h if o is not None else None  # noqa: E731
+        rc = load_library().authjx_phase_create(ctx._h if ctx is not None else None, ptr(rules), ptr(selectors),
+                                                ptr(prog), int(text_stride), int(out_stride), C.byref(h))
+        _check(rc, "authjx_phase_create")
+        self._h = h
+        self.ctx, self.rules, self.selectors, self.prog = ctx, rules, selectors, prog
+        self.text_stride, self.out_stride = int(text_stride), int(out_stride)
+        self.n_outputs = int(load_library().authjx_phase_outputs(h))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                load_library().authjx_phase_free(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
 # -------------------------------------------------------------------------------------
 # jsonexp.Expression adapter
 # -------------------------------------------------------------------------------------
@@ -683,6 +743,49 @@ class Batcher:
             raise BatchTimeout("authjx_batcher_eval: deadline passed")
         _check(rc, "authjx_batcher_eval")
         return list(tri), list(err)
+
+    def phase(self, phase: "Phase", doc, timeout_s: float = 0.0, out_text=None, out=None):
+        """authjx_batcher_phase: (tri-states, error indices, [bytes | None per output]) of one
+        document: the decision of the phase's rules and every output of its render program
+        (None: the device declined it, RENDER_UNRENDERED). out_text (u8[out_stride]) / out
+        (u32[n_outputs][3]): the caller's own buffers to render into, else fresh ones."""
+        d = _b(doc)
+        nt = max(1, len(phase.rules.offsets))
+        tri = (C.c_uint8 * nt)()
+        err = (C.c_int32 * nt)()
+        if out_text is None:
+            out_text = np.zeros(phase.out_stride, dtype=np.uint8)
+        if out is None:
+            out = np.zeros((max(phase.n_outputs, 1), 3), dtype=np.uint32)
+        rc = load_library().authjx_batcher_phase(self._h, phase._h, d, len(d), int(timeout_s * 1e6), tri, err,
+                                                 C.c_void_p(out_text.ctypes.data), C.c_void_p(out.ctypes.data))
+        if rc == -5:
+            raise BatchTimeout("authjx_batcher_phase: deadline passed")
+        _check(rc, "authjx_batcher_phase")
+        vals = [out_text[int(s):int(s) + int(ln)].tobytes() if (int(st) & 0xFF) == RENDER_OK else None
+                for s, ln, st in out[:phase.n_outputs]]
+        return list(tri), list(err), vals
+
+    def phase_loadgen(self, phases, phase_of_req, arena, offs, lens, threads: int = 64):
+        """Profiling: authjx_debug_phase_loadgen, `threads` native producer threads calling
+        authjx_batcher_phase one request at a time. Returns (per-request latency ns, first
+        result per request, 64-bit FNV-1a of each request's rendered outputs, wall ns)."""
+        L = load_library()
+        L.authjx_debug_phase_loadgen.argtypes = [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+        n = len(lens)
+        parr = (C.c_void_p * len(phases))(*[p._h.value for p in phases])
+        por = np.ascontiguousarray(phase_of_req, dtype=np.uint32)
+        ar = np.ascontiguousarray(arena, dtype=np.uint8)
+        of = np.ascontiguousarray(offs, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint32)
+        lat = np.zeros(n, dtype=np.uint64)
+        tri = np.zeros(n, dtype=np.uint8)
+        hsh = np.zeros(n, dtype=np.uint64)
+        wall = C.c_uint64()
+        _check(L.authjx_debug_phase_loadgen(self._h, parr, por.ctypes.data, ar.ctypes.data, of.ctypes.data,
+                                            ln.ctypes.data, n, threads, lat.ctypes.data, tri.ctypes.data,
+                                            hsh.ctypes.data, C.byref(wall)), "authjx_debug_phase_loadgen")
+        return lat, tri, hsh, wall.value
 
     def loadgen(self, rulesets, set_of_req, arena, offs, lens, threads: int = 64):
         """Profiling: `threads` native producer threads push every request through this

@@ -431,6 +431,58 @@ int authjx_render_batch(authjx_ctx* ctx, const authjx_render* prog, const uint8_
                         uint32_t values_stride, const uint8_t* text, uint32_t text_stride, uint8_t* out_text,
                         uint32_t out_stride, authjx_rendered* out);
 
+/* authjx_render_batch_device for a batch of several AuthConfigs: request r renders
+ * progs[d_prog_of_req[r]] (device u32[n]; may be NULL when n_progs is 1: every request
+ * renders progs[0]). AUTHJX_RENDER_NO_PROGRAM, or any entry
+ * that is not below n_progs: the request reads nothing and writes nothing, neither its
+ * output slot nor its records. Output k of request r is d_out[r * records_stride + k]
+ * (records_stride >= the largest n_outputs; a program's records beyond its own n_outputs
+ * are not written), its values d_values[r * values_stride ...] (values_stride >= the
+ * largest n_slots). The table of program pointers is uploaded on `stream`. The checks of
+ * authjx_render_batch_device, and AUTHJX_EINVAL as well when values_stride or
+ * records_stride is below what a program needs, a program is NULL or of another device, or
+ * n_progs > 1 and d_prog_of_req is NULL. */
+#define AUTHJX_RENDER_NO_PROGRAM 0xFFFFFFFFu
+int authjx_render_batch_multi_device(authjx_ctx* ctx, const authjx_render* const* progs, uint32_t n_progs,
+                                     const uint32_t* d_prog_of_req, const uint8_t* d_arena, const uint64_t* d_offs,
+                                     const uint32_t* d_lens, uint32_t n, const authjx_value* d_values,
+                                     uint32_t values_stride, const uint8_t* d_text, uint32_t text_stride,
+                                     uint8_t* d_out_text, uint32_t out_stride, authjx_rendered* d_out,
+                                     uint32_t records_stride, void* stream);
+
+/* ---- micro-batcher: a phase's response outputs with each decision -------------------
+ * One AuthConfig as the serving path sees it: `rules` (authjx_compile or _forest: what
+ * authjx_batcher_eval takes), `selectors` (authjx_compile, patterns {path, EQ, ""}, root -1:
+ * slot k = pattern k) and the render program over those slots. Borrowed, not owned: free the
+ * phase before any of the three. text_stride: bytes of built text per request (modifier
+ * chains, "#." lists); 0: such values come back AUTHJX_JSON_UNSUPPORTED and their outputs
+ * AUTHJX_RENDER_UNRENDERED, as after authjx_select_batch. out_stride: bytes of rendered
+ * text per request. AUTHJX_EINVAL: a NULL argument; `selectors` has more than one tree, no
+ * pattern, or fewer patterns than `prog` has slots; out_stride is 0 or no multiple of 16; the objects'
+ * devices differ. AUTHJX_ELIMIT: out_stride or text_stride above 65536 (pinned staging per
+ * request). */
+typedef struct authjx_phase authjx_phase;
+int authjx_phase_create(authjx_ctx* ctx, const authjx_ruleset* rules, const authjx_ruleset* selectors,
+                        const authjx_render* prog, uint32_t text_stride, uint32_t out_stride, authjx_phase** out);
+void authjx_phase_free(authjx_phase* ph);
+uint32_t authjx_phase_outputs(const authjx_phase* ph);
+/* Blocking, like authjx_batcher_eval, and batched with its requests: the decision (n_trees
+ * entries) and, rendered from the same staged copy of the document in the same batch on the
+ * same stream, every output of the program, whatever the decision (which outputs apply —
+ * response headers after a grant, denyWith after a denial — is the caller's fold):
+ * out[k] = {start, len, status} into out_text[0, out_stride), authjx_phase_outputs(ph)
+ * records. out_text is written up to the end of the last output; its bytes past that, and
+ * both buffers when the call does not return AUTHJX_OK (AUTHJX_ETIMEDOUT, a failed batch),
+ * are left as they were. Requests of phases with different strides share a batch but not
+ * a select / render launch.
+ * Lifetime: the call returns after its batch's worker has synchronized the stream, so no
+ * kernel reads a phase's ruleset, selectors or program once the last call on that phase
+ * has returned; authjx_free / authjx_render_free then wait as they always do, and
+ * authjx_shutdown destroys the batchers first. */
+int authjx_batcher_phase(authjx_batcher* b, const authjx_phase* ph, const uint8_t* doc, size_t len,
+                         uint64_t timeout_us, uint8_t* out_tristate, int32_t* out_err_idx,
+                         uint8_t* out_text, authjx_rendered* out);
+
 #ifdef __cplusplus
 }
 #endif
