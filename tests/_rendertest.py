@@ -1,6 +1,6 @@
-"""TEST-ONLY helpers of the render tests (tests/test_render_host.py, tests/test_gpu_render.py):
-a ctypes binding of tests/native/libajx_rendertest.so (host build of
-authorino_amd/csrc/ajx_render.h), the Python mirror of a render program (response.py's host
+"""TEST-ONLY helpers of the render tests (tests/test_render_host.py, tests/test_gpu_render.py,
+tests/_rendervalues.py): a ctypes binding of tests/native/libajx_rendertest.so (host build of
+authorino_amd/csrc/ajx_render.h) or of such a library at another path, the Python mirror of a render program (response.py's host
 functions per op: the expected bytes), selected values from the oracle, and the fuzz and
 decline inputs both test files share. Not product code."""
 from __future__ import annotations
@@ -30,19 +30,25 @@ def make(target: str) -> str:
     return os.path.join(NATIVE, target)
 
 
+def load(path: str):
+    """The ctypes binding of a host build of render_host.cpp (the one render.mk makes, or a
+    library a test compiled itself)."""
+    L = C.CDLL(path)
+    L.rt_compile.argtypes = [C.POINTER(_RenderOutput), C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t,
+                             C.POINTER(C.c_int)]
+    L.rt_compile.restype = C.c_void_p
+    L.rt_free.argtypes = [C.c_void_p]
+    L.rt_max_depth.restype = C.c_int
+    L.rt_render.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                               C.c_void_p, C.c_uint32, C.c_void_p]
+    L.rt_render.restype = C.c_int
+    return L
+
+
 def lib():
     global _L
     if _L is None:
-        L = C.CDLL(make("libajx_rendertest.so"))
-        L.rt_compile.argtypes = [C.POINTER(_RenderOutput), C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t,
-                                 C.POINTER(C.c_int)]
-        L.rt_compile.restype = C.c_void_p
-        L.rt_free.argtypes = [C.c_void_p]
-        L.rt_max_depth.restype = C.c_int
-        L.rt_render.argtypes = [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
-                                                   C.c_void_p, C.c_uint32, C.c_void_p]
-        L.rt_render.restype = C.c_int
-        _L = L
+        _L = load(make("libajx_rendertest.so"))
     return _L
 
 
@@ -65,19 +71,21 @@ def c_outputs(outputs):
 
 
 class HostProgram:
-    """build_render_program (what authjx_render_compile runs) on the CPU."""
+    """build_render_program (what authjx_render_compile runs) on the CPU, by the library
+    `L` (load()) or the tree's own."""
 
-    def __init__(self, outputs, n_slots):
+    def __init__(self, outputs, n_slots, L=None):
         oarr, keep = c_outputs(outputs)
         err = C.create_string_buffer(256)
         rc = C.c_int(0)
-        self._h = lib().rt_compile(oarr, len(outputs), n_slots, err, 256, C.byref(rc))
+        self._L = L if L is not None else lib()
+        self._h = self._L.rt_compile(oarr, len(outputs), n_slots, err, 256, C.byref(rc))
         self.rc, self.error = rc.value, err.value.decode()
         self.n_outputs, self.n_slots = len(outputs), n_slots
 
     def __del__(self):
         if getattr(self, "_h", None):
-            lib().rt_free(self._h)
+            self._L.rt_free(self._h)
             self._h = None
 
 
@@ -100,7 +108,7 @@ def host_render(prog: HostProgram, docs, values, text, out_stride, out_text=None
     rec = np.zeros((n, max(prog.n_outputs, 1), 3), dtype=np.uint32)
     if text is not None:
         text = np.ascontiguousarray(text, dtype=np.uint8)
-    rc = lib().rt_render(prog._h, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, n, values.ctypes.data,
+    rc = prog._L.rt_render(prog._h, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, n, values.ctypes.data,
                          values.shape[1], text.ctypes.data if text is not None else None,
                          text.shape[1] if text is not None else 0, out_text.ctypes.data, out_stride,
                          rec.ctypes.data)
