@@ -17,7 +17,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libauthjx.so")
 INCLUDE_H = os.path.join(HERE, "..", "include", "authjx.h")
 SOURCES = ["ajx_regex.cpp", "ajx_compiler.cpp", "ajx_api.cpp", "ajx_index.cpp", "ajx_producer.cpp", "ajx_kernels.hip", "ajx_lean.hip",
-           "ajx_render_api.cpp", "ajx_render.hip", "ajx_batcher_api.cpp", "ajx_phase_api.cpp"]
+           "ajx_render_api.cpp", "ajx_render.hip", "ajx_batcher_api.cpp", "ajx_phase_api.cpp",
+           "ajx_render_gated_api.cpp"]
 ARCH = os.environ.get("AUTHJX_ARCH", "gfx950")
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 

@@ -60,6 +60,7 @@ struct BatchReq {
     const PhaseFacts* phase = nullptr;
     uint8_t* out_text = nullptr;
     void* out_rec = nullptr;
+    void* out_verdict = nullptr;  // a gated phase's verdict (two words), or null
     // completion. Wake mode 0: this request's condition variable; 1: `flag`, then one
     // broadcast on the core's completion word for the whole batch; 2: `flag` as this
     // request's own futex word; 3: as 2, woken as node `idx` of a binary tree over the batch

@@ -74,11 +74,15 @@ struct authjx_batcher {
         const ajx::PhasePlan plan = ajx::plan_phases(reqs);
         const uint32_t m = plan.n(), vs = plan.values_stride, rs = plan.records_stride;
         const size_t o_poffs = lay.add((size_t)m * 8), o_plens = lay.add((size_t)m * 4);
-        const size_t o_por = lay.add((size_t)m * 4), o_ptab = lay.add(plan.progs.size() * sizeof(uint8_t*));
-        const size_t o_psor = lay.add((size_t)m * 4);
+        // (a batch with a gated phase request: the gates' blobs behind the programs' in the
+        // table, each subset position's tri-state row, and a verdict per position)
+        const bool gated = plan.render_gated != nullptr;
+        const size_t np = plan.progs.size();
+        const size_t o_por = lay.add((size_t)m * 4), o_ptab = lay.add((gated ? 2 : 1) * np * sizeof(uint8_t*));
+        const size_t o_psor = lay.add((size_t)m * 4), o_ptor = lay.add(gated ? (size_t)m * 4 : 0);
         const size_t in_bytes = lay.total();  // (the outputs after it: host side only)
         const size_t o_tri = lay.add((size_t)n * nt), o_err = lay.add((size_t)n * nt * 4);
-        const size_t o_rec = lay.add((size_t)m * rs * 12);
+        const size_t o_rec = lay.add((size_t)m * rs * 12), o_ver = lay.add(gated ? (size_t)m * 8 : 0);
         ajx::StageLayout mid;
         const size_t o_val = mid.add((size_t)m * vs * 12);
         std::vector<size_t> o_text(plan.groups.size()), o_out(plan.groups.size());
@@ -114,7 +118,11 @@ struct authjx_batcher {
             }
             std::memcpy(h + o_por, plan.prog_of.data(), (size_t)m * 4);
             const uint8_t** pt = (const uint8_t**)(h + o_ptab);
-            for (size_t k = 0; k < plan.progs.size(); k++) pt[k] = (const uint8_t*)plan.progs[k];
+            for (size_t k = 0; k < np; k++) pt[k] = (const uint8_t*)plan.progs[k];
+            if (gated) {
+                for (size_t k = 0; k < np; k++) pt[np + k] = (const uint8_t*)plan.gates[k];
+                std::memcpy(h + o_ptor, plan.tri_row.data(), (size_t)m * 4);
+            }
             for (const ajx::PhaseGroup& g : plan.groups)
                 std::memcpy(h + o_psor + (size_t)g.first * 4, g.set_of.data(), (size_t)g.count * 4);
         }
@@ -143,6 +151,17 @@ struct authjx_batcher {
             if (rc2 != AUTHJX_OK) {
                 (void)hipStreamSynchronize(L.stream);  // (the evaluation queued above reads the lane's buffers)
                 return rc2;
+            }
+            // the tri-states are read where the evaluation above left them (the lane's mapped
+            // output part), before anything is copied back: one gated launch for the group
+            if (gated) {
+                HIP_OK((hipError_t)plan.render_gated(
+                    (const uint8_t* const*)(in + o_ptab), (uint32_t)np, (const uint32_t*)(in + o_por) + g.first, in,
+                    d_offs, d_lens, g.count, (const uint32_t*)d_val, vs, d_text, g.text_stride, out_dev + o_out[gi],
+                    g.out_stride, (uint32_t*)(out_dev + o_rec) + (size_t)g.first * rs * 3, rs, out_dev + o_tri, nt,
+                    (const uint32_t*)(in + o_ptor) + g.first, (uint32_t*)(out_dev + o_ver) + (size_t)g.first * 2,
+                    L.stream));
+                continue;
             }
             const ajx::PhaseRender render = reqs[plan.req[g.first]]->phase->render;
             HIP_OK((hipError_t)render((const uint8_t* const*)(in + o_ptab), (uint32_t)plan.progs.size(),
@@ -175,9 +194,13 @@ struct authjx_batcher {
         }
         for (size_t gi = 0; gi < plan.groups.size(); gi++) {
             const ajx::PhaseGroup& g = plan.groups[gi];
-            for (uint32_t j = 0; j < g.count; j++)
+            for (uint32_t j = 0; j < g.count; j++) {
                 ajx::deliver_phase(*reqs[plan.req[g.first + j]], h + o_out[gi] + (size_t)j * g.out_stride,
                                    (const uint32_t*)(h + o_rec) + (size_t)(g.first + j) * rs * 3);
+                if (gated)
+                    ajx::deliver_verdict(*reqs[plan.req[g.first + j]],
+                                         (const uint32_t*)(h + o_ver) + (size_t)(g.first + j) * 2);
+            }
         }
         return AUTHJX_OK;
     }
@@ -295,6 +318,27 @@ int authjx_batcher_phase(authjx_batcher* b, const authjx_phase* ph, const uint8_
     r.phase = &ph->f;
     r.out_text = out_text;
     r.out_rec = out;
+    return b->core->submit(r);
+}
+
+int authjx_batcher_phase_gated(authjx_batcher* b, const authjx_phase* ph, const uint8_t* doc, size_t len,
+                               uint64_t timeout_us, uint8_t* out_tristate, int32_t* out_err_idx, uint8_t* out_text,
+                               authjx_rendered* out, authjx_verdict* out_verdict) {
+    if (!b || !ph || (!doc && len) || !out_tristate || len >= (1ull << 32)) return AUTHJX_EINVAL;
+    if (!out_text || (ph->f.n_outputs && !out) || ph->device != b->ctx->device) return AUTHJX_EINVAL;
+    if (!ph->f.gates || !ph->f.render_gated) return AUTHJX_EINVAL;  // (an ungated phase)
+    ajx::BatchReq r;
+    r.rs = ph->rules;
+    r.n_out = ph->rules->c.n_trees;
+    r.doc = doc;
+    r.len = len;
+    r.deadline_ns = timeout_us ? ajx::mono_ns() + timeout_us * 1000ull : 0;
+    r.out_tri = out_tristate;
+    r.out_err = out_err_idx;
+    r.phase = &ph->f;
+    r.out_text = out_text;
+    r.out_rec = out;
+    r.out_verdict = out_verdict;
     return b->core->submit(r);
 }
 

@@ -30,6 +30,16 @@ using PhaseRender = int (*)(const uint8_t* const* progs, uint32_t n_progs, const
                             uint8_t* out_text, uint32_t out_stride, uint32_t* out, uint32_t records_stride,
                             void* stream);
 
+// The gated render launch (ajx::launch_render_gated) in plain types: tables holds the
+// n_progs program blobs, then their n_progs gates blobs (null: ungated); tri / tri_stride /
+// tri_of_req: the batch's tri-states and each request's row; verdicts: two words per request.
+using PhaseRenderGated = int (*)(const uint8_t* const* tables, uint32_t n_progs, const uint32_t* prog_of_req,
+                                 const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                                 const uint32_t* values, uint32_t values_stride, const uint8_t* text,
+                                 uint32_t text_stride, uint8_t* out_text, uint32_t out_stride, uint32_t* out,
+                                 uint32_t records_stride, const uint8_t* tri, uint32_t tri_stride,
+                                 const uint32_t* tri_of_req, uint32_t* verdicts, void* stream);
+
 // what the plan reads of a phase (authjx_phase holds one)
 struct PhaseFacts {
     const void* selectors = nullptr;  // the selector ruleset
@@ -38,6 +48,10 @@ struct PhaseFacts {
     uint32_t n_patterns = 0;          // of the selector ruleset: the values the select writes per request
     uint32_t n_outputs = 0;           // of the program
     uint32_t text_stride = 0, out_stride = 0;
+    // a gated phase (authjx_phase_create_gated): its gates' blob in device memory and the
+    // gated launch; null for an ungated one
+    const void* gates = nullptr;
+    PhaseRenderGated render_gated = nullptr;
 };
 
 struct PhaseGroup {
@@ -49,8 +63,12 @@ struct PhaseGroup {
 
 struct PhasePlan {
     std::vector<uint32_t> req;       // subset position j -> index in the batch
-    std::vector<const void*> progs;  // the batch's distinct programs
-    std::vector<uint32_t> prog_of;   // per subset position: index into progs
+    std::vector<const void*> progs;  // the batch's distinct {program, gates} pairs: the programs
+    std::vector<const void*> gates;  // ... and their gates (null: ungated), entry for entry
+    std::vector<uint32_t> prog_of;   // per subset position: index into progs / gates
+    std::vector<uint32_t> tri_row;   // per subset position: its row in the batch's tri-state array
+    PhaseRenderGated render_gated = nullptr;  // set when a request of the batch is gated: every
+                                              // group then takes the gated launch
     std::vector<PhaseGroup> groups;
     uint32_t values_stride = 0, records_stride = 0;  // the largest n_patterns / n_outputs
     uint32_t n() const { return (uint32_t)req.size(); }
@@ -67,13 +85,19 @@ inline PhasePlan plan_phases(const std::vector<BatchReq*>& reqs) {
         return x.text_stride != y.text_stride ? x.text_stride < y.text_stride : x.out_stride < y.out_stride;
     });
     p.prog_of.resize(p.req.size());
+    p.tri_row = p.req;  // (the evaluation writes request i's tri-states at row i)
     for (uint32_t j = 0; j < p.n(); j++) {
         const PhaseFacts& f = *reqs[p.req[j]]->phase;
         p.values_stride = std::max(p.values_stride, f.n_patterns);
         p.records_stride = std::max(p.records_stride, f.n_outputs);
-        const auto it = std::find(p.progs.begin(), p.progs.end(), f.prog);
-        p.prog_of[j] = (uint32_t)(it - p.progs.begin());
-        if (it == p.progs.end()) p.progs.push_back(f.prog);
+        uint32_t k = 0;
+        while (k < p.progs.size() && !(p.progs[k] == f.prog && p.gates[k] == f.gates)) k++;
+        p.prog_of[j] = k;
+        if (k == p.progs.size()) {
+            p.progs.push_back(f.prog);
+            p.gates.push_back(f.gates);
+        }
+        if (f.gates && !p.render_gated) p.render_gated = f.render_gated;
         if (p.groups.empty() || p.groups.back().text_stride != f.text_stride ||
             p.groups.back().out_stride != f.out_stride) {
             PhaseGroup g;
@@ -103,6 +127,11 @@ inline void deliver_phase(const BatchReq& r, const uint8_t* slot, const uint32_t
     }
     if (end && r.out_text) std::memcpy(r.out_text, slot, end);
     if (f.n_outputs && r.out_rec) std::memcpy(r.out_rec, rec, 12u * (size_t)f.n_outputs);
+}
+
+// A gated phase request's verdict (two words: verdict, denied_by) to its caller.
+inline void deliver_verdict(const BatchReq& r, const uint32_t* verdict) {
+    if (r.phase->gates && r.out_verdict) std::memcpy(r.out_verdict, verdict, 8);
 }
 
 }  // namespace ajx

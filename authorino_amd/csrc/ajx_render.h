@@ -5,6 +5,7 @@
 //   templates             ReplaceJSONPlaceholders: Result.String()    (pkg/json/json.go:96-151)
 //   response.DynamicJSON  json.Marshal of a map, then StringifyJSON   (dynamic_json.go:20-31,
 //                                                                       json.go:153-159)
+//   denyWith              StringifyJSON of a resolved value                (auth_pipeline.go:581-608)
 // as authorino_amd/response.py restates them (result_string, go_sprint_v, go_json_marshal,
 // stringify_json). Per-request logic as AJX_HD functions: __device__ in ajx_render.hip,
 // plain inline functions in the test-only host build (tests/native/render_host.cpp).
@@ -30,9 +31,12 @@ constexpr uint32_t kRenderMagic = 0x52444E52u;
 constexpr uint8_t kRenderValText = 4;
 
 // ops (AUTHJX_R_* of include/authjx.h)
-enum : uint32_t { R_LIT = 0, R_STRING = 1, R_STRING_ESC = 2, R_SPRINT = 3, R_MARSHAL = 4, R_OP_COUNT = 5 };
+enum : uint32_t {
+    R_LIT = 0, R_STRING = 1, R_STRING_ESC = 2, R_SPRINT = 3, R_MARSHAL = 4, R_STRINGIFY = 6, R_STRING_UTF8 = 7,
+    R_OP_COUNT = 8  // (5 is not assigned)
+};
 // output status (AUTHJX_RENDER_*)
-constexpr uint32_t kRenderOk = 0, kRenderUnrendered = 1;
+constexpr uint32_t kRenderOk = 0, kRenderUnrendered = 1, kRenderSkipped = 2;
 
 struct RenderHdr {
     uint32_t magic, n_outputs, n_slots, n_ops;
@@ -264,6 +268,39 @@ AJX_HD bool render_escaped(RenderOut& w, StrSrc* s) {
     }
 }
 
+// The stream's bytes as they are. False on bytes that are not UTF-8 (utf8.DecodeRune's
+// accepted forms, as render_escaped reads them): under StringifyJSON Go writes U+FFFD there.
+AJX_HD bool render_utf8(RenderOut& w, StrSrc* s) {
+    for (;;) {
+        const int c = s->next();
+        if (c < 0) return true;
+        if (!w.ok) return false;
+        w.put((uint32_t)c);
+        if (c < 0x80) continue;
+        const uint32_t b0 = (uint32_t)c;
+        int need = 0;
+        uint32_t lo = 0x80, hi = 0xBF;
+        if (b0 >= 0xC2 && b0 <= 0xDF) need = 2;
+        else if (b0 >= 0xE0 && b0 <= 0xEF) {
+            need = 3;
+            if (b0 == 0xE0) lo = 0xA0;
+            if (b0 == 0xED) hi = 0x9F;
+        } else if (b0 >= 0xF0 && b0 <= 0xF4) {
+            need = 4;
+            if (b0 == 0xF0) lo = 0x90;
+            if (b0 == 0xF4) hi = 0x8F;
+        }
+        if (!need) return false;
+        for (int k = 1; k < need; k++) {
+            const int x = s->next();
+            if (x < (int)lo || x > (int)hi) return false;
+            w.put((uint32_t)x);
+            lo = 0x80;
+            hi = 0xBF;
+        }
+    }
+}
+
 // a string's contents [a, b) (between the quotes): raw bytes for %v, encoded for json
 AJX_HD int render_str(RenderOut& w, const uint8_t* d, uint32_t a, uint32_t b, bool esc, bool js) {
     StrSrc s;
@@ -422,7 +459,20 @@ AJX_HD int render_value(RenderOut& w, uint32_t op, const uint8_t* src, const Val
         for (int c; (c = s.next()) >= 0 && w.ok;) w.put((uint32_t)c);
         return RR_OK;
     }
-    const bool js = op == R_MARSHAL;
+    if (op == R_STRING_UTF8 || (op == R_STRINGIFY && v.type != T_NULL && v.type != T_JSON)) {
+        // StringifyJSON of a scalar: Marshal's text read back by Result.String(). A number goes
+        // through float64 whatever its spelling and comes out in eq's 'f' layout (StrSrc)
+        StrSrc s;
+        if (op == R_STRINGIFY && v.type == T_NUMBER && v.esc != kValCount) {
+            if (!s.init_num<true>(src, v.start, v.end)) return RR_DECLINE;
+            if (s.num.kind == NumCanon::K_PINF || s.num.kind == NumCanon::K_NINF || s.num.kind == NumCanon::K_NAN)
+                return RR_POISON;
+        } else if (!string_of<true>(src, v, &s)) {
+            return RR_DECLINE;
+        }
+        return render_utf8(w, &s) ? RR_OK : RR_DECLINE;
+    }
+    const bool js = op == R_MARSHAL || op == R_STRINGIFY;
     switch (v.type) {
         case T_STRING: return render_str(w, src, v.start + 1, v.end - 1, (v.esc & 1) != 0, js);
         case T_NUMBER:
@@ -436,7 +486,9 @@ AJX_HD int render_value(RenderOut& w, uint32_t op, const uint8_t* src, const Val
             if (s0 >= v.end || (src[s0] != '{' && src[s0] != '[')) return RR_DECLINE;
             return render_container(w, src, s0, v.end, js, st);
         }
-        case T_NULL: w.put_str(js ? "null" : "<nil>"); return RR_OK;
+        case T_NULL:
+            if (op != R_STRINGIFY) w.put_str(js ? "null" : "<nil>");
+            return RR_OK;
         default: return RR_DECLINE;
     }
 }
@@ -444,9 +496,14 @@ AJX_HD int render_value(RenderOut& w, uint32_t op, const uint8_t* src, const Val
 // Every output of one request. vals: the request's values, three words each {start, len,
 // type | esc << 8}; text: its text slot or nullptr; out: its output slot (16-byte aligned,
 // out_cap a multiple of 16); res: n_outputs records of three words {start, len, status}.
-AJX_HD void render_request(const uint8_t* prog, const uint8_t* doc, uint32_t doc_len, const uint32_t* vals,
-                           const uint8_t* text, uint32_t text_cap, uint8_t* out, uint32_t out_cap, uint32_t* res,
-                           const RenderStack& st) {
+// gate(k): kRenderOk when output k renders, else the status it gets instead
+// (kRenderUnrendered, kRenderSkipped): such an output appends nothing, reads none of its ops
+// or values (the gate's own reads apart: ajx_verdict.h gate_output loads the output's {on,
+// when} pair and at most one tri-state byte) and leaves the writer as it found it.
+template <class Gate>
+AJX_HD void render_request_under(const uint8_t* prog, const uint8_t* doc, uint32_t doc_len, const uint32_t* vals,
+                                 const uint8_t* text, uint32_t text_cap, uint8_t* out, uint32_t out_cap, uint32_t* res,
+                                 const RenderStack& st, const Gate& gate) {
     const RenderHdr* h = reinterpret_cast<const RenderHdr*>(prog);
     const uint32_t* begin = reinterpret_cast<const uint32_t*>(prog + h->off_begin);
     const RenderOp* ops = reinterpret_cast<const RenderOp*>(prog + h->off_ops);
@@ -456,8 +513,11 @@ AJX_HD void render_request(const uint8_t* prog, const uint8_t* doc, uint32_t doc
     for (uint32_t k = 0; k < h->n_outputs; k++) {
         RenderMark mark;
         mark.take(w);
+        const uint32_t gated = gate(k);
         int rc = RR_OK;
-        for (uint32_t q = begin[k]; q < begin[k + 1] && rc == RR_OK; q++) {
+        // (an output that does not apply reads neither its op range nor an op)
+        const uint32_t q0 = gated == kRenderOk ? begin[k] : 0u, q1 = gated == kRenderOk ? begin[k + 1] : 0u;
+        for (uint32_t q = q0; q < q1 && rc == RR_OK; q++) {
             const RenderOp op = ops[q];
             if (op.op == R_LIT) {
                 w.put_bytes(lits + op.lit_off, op.lit_len);
@@ -484,9 +544,19 @@ AJX_HD void render_request(const uint8_t* prog, const uint8_t* doc, uint32_t doc
         if (rc != RR_OK) mark.restore(&w);
         res[3 * k + 0] = mark.pos;
         res[3 * k + 1] = w.pos - mark.pos;
-        res[3 * k + 2] = rc == RR_DECLINE ? kRenderUnrendered : kRenderOk;
+        res[3 * k + 2] = gated != kRenderOk ? gated : rc == RR_DECLINE ? kRenderUnrendered : kRenderOk;
     }
     w.flush();
+}
+
+struct RenderUngated {
+    AJX_HD uint32_t operator()(uint32_t) const { return kRenderOk; }
+};
+
+AJX_HD void render_request(const uint8_t* prog, const uint8_t* doc, uint32_t doc_len, const uint32_t* vals,
+                           const uint8_t* text, uint32_t text_cap, uint8_t* out, uint32_t out_cap, uint32_t* res,
+                           const RenderStack& st) {
+    render_request_under(prog, doc, doc_len, vals, text, text_cap, out, out_cap, res, st, RenderUngated{});
 }
 
 // prog_of_req entry of a request that renders nothing (AUTHJX_RENDER_NO_PROGRAM)

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/authjx.h"
 #include "ajx_hostbuf.h"
 
@@ -12,6 +14,15 @@ struct authjx_render {
     int device = 0;
     ajx::DeviceBuf d_prog;
     uint32_t n_outputs = 0, n_slots = 0;
+};
+
+// the gates of a render program (authjx_gates_compile): the blob on the device for the gated
+// kernel and on the host for authjx_verdict_of
+struct authjx_gates {
+    int device = 0;
+    ajx::DeviceBuf d_blob;
+    std::vector<uint8_t> blob;
+    uint32_t n_outputs = 0, n_trees = 0;
 };
 
 // the context's device and its own stream (ajx_api.cpp)
@@ -38,5 +49,15 @@ hipError_t launch_render_multi(const uint8_t* const* d_progs, uint32_t n_progs, 
                                const uint32_t* values, uint32_t values_stride, const uint8_t* text,
                                uint32_t text_stride, uint8_t* out_text, uint32_t out_stride, uint32_t* out,
                                uint32_t records_stride, hipStream_t stream);
+
+// The gated kernel: d_tables holds the n_progs program blobs, then their n_progs gates
+// blobs (nullptr: ungated). tri: u8 tri-states, row (tri_of_req ? tri_of_req[r] : r) of
+// tri_stride bytes for request r; verdicts: two words per request or nullptr.
+hipError_t launch_render_gated(const uint8_t* const* d_tables, uint32_t n_progs, const uint32_t* prog_of_req,
+                               const uint8_t* arena, const uint64_t* offs, const uint32_t* lens, uint32_t n,
+                               const uint32_t* values, uint32_t values_stride, const uint8_t* text,
+                               uint32_t text_stride, uint8_t* out_text, uint32_t out_stride, uint32_t* out,
+                               uint32_t records_stride, const uint8_t* tri, uint32_t tri_stride,
+                               const uint32_t* tri_of_req, uint32_t* verdicts, hipStream_t stream);
 
 }  // namespace ajx

@@ -23,7 +23,8 @@ inline int build_render_program(const authjx_render_output* outs, uint32_t n_out
         for (uint32_t q = 0; q < outs[k].n_ops; q++) {
             const authjx_render_op& op = outs[k].ops[q];
             const std::string at = "output " + std::to_string(k) + " op " + std::to_string(q);
-            if (op.op > AUTHJX_R_MARSHAL) { *err = at + ": unknown op"; return AUTHJX_EINVAL; }
+            // (5 is not assigned)
+            if (op.op > AUTHJX_R_STRING_UTF8 || op.op == 5) { *err = at + ": unknown op"; return AUTHJX_EINVAL; }
             uint32_t off = 0, len = 0, slot = 0;
             if (op.op == AUTHJX_R_LIT) {
                 if (!op.lit && op.lit_len) { *err = at + ": no literal"; return AUTHJX_EINVAL; }

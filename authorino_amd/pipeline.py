@@ -138,6 +138,61 @@ class AuthResult:
     metadata: Dict[str, object] = field(default_factory=dict)  # success: dynamic metadata
 
 
+@dataclass
+class GatePlan:
+    """What authjx_gates_compile takes (include/authjx.h): the tree of the AuthConfig's
+    `when`, the evaluators [(when_tree, rules_tree, priority)] in priority order and the
+    render program's outputs [(GATE_*, when_tree)]; a tree of -1 stands for none."""
+
+    top: int
+    evaluators: List[Tuple[int, int, int]]
+    outputs: List[Tuple[int, int]]
+    n_trees: int
+
+
+V_SKIPPED, V_GRANTED, V_DENIED, V_UNDECIDED = range(4)  # AUTHJX_V_*
+GATE_ALWAYS, GATE_GRANTED, GATE_DENIED = range(3)       # AUTHJX_GATE_*
+_F, _T, _E, _U = range(4)                                # AUTHJX_F / T / E / UNDECIDED
+
+
+def verdict_of(tri_row, plan: GatePlan) -> Tuple[int, int]:
+    """The executable specification of the verdict fold (ajx_verdict.h runs it on the
+    device and behind authjx_verdict_of): (verdict, denied_by) of one request's tri-states,
+    as AuthPipelineBatch.evaluate decides it level by level."""
+    tri = lambda t: _T if t < 0 else int(tri_row[t])  # noqa: E731
+    top = tri(plan.top)
+    if top == _U:
+        return V_UNDECIDED, -1
+    if top != _T:
+        return V_SKIPPED, -1
+    for prio in sorted({p for _, _, p in plan.evaluators}):
+        level = [(i, w, r) for i, (w, r, p) in enumerate(plan.evaluators) if p == prio]
+        if any(tri(t) == _U for _, w, r in level for t in (w, r)):
+            return V_UNDECIDED, -1
+        for i, w, r in level:
+            if tri(w) == _T and r >= 0 and tri(r) != _T:
+                return V_DENIED, i
+    return V_GRANTED, -1
+
+
+def output_status_of(tri_row, plan: GatePlan, verdict: int, k: int) -> int:
+    """RENDER_OK when output k renders under `verdict`, else the status it gets instead
+    (RENDER_UNRENDERED, RENDER_SKIPPED)."""
+    from .response import RENDER_OK, RENDER_SKIPPED, RENDER_UNRENDERED
+
+    on, when = plan.outputs[k]
+    if on == GATE_ALWAYS:
+        return RENDER_OK
+    if verdict == V_UNDECIDED:
+        return RENDER_UNRENDERED
+    if on == GATE_DENIED:
+        return RENDER_OK if verdict == V_DENIED else RENDER_SKIPPED
+    if verdict != V_GRANTED:
+        return RENDER_SKIPPED
+    w = _T if when < 0 else int(tri_row[when])
+    return RENDER_OK if w == _T else RENDER_UNRENDERED if w == _U else RENDER_SKIPPED
+
+
 def _paths_select_authorization(paths) -> bool:
     return any(p == "auth.authorization" or p.startswith("auth.authorization.") for p in paths)
 
@@ -152,10 +207,19 @@ def _selects_authorization(expr: Optional[jsonexp.Expression]) -> bool:
 class AuthPipelineBatch:
     """The `when` gates + authorization phase of AuthPipeline.Evaluate for a batch."""
 
-    def __init__(self, auth_config: AuthConfig, device: int = 0, ctx=None):
+    def __init__(self, auth_config: AuthConfig, device: int = 0, ctx=None, gated: bool = False):
+        """gated: take the verdict and the outputs that apply under it (response headers
+        after a grant, denyWith after a denial) from ONE gated render on the device
+        (authjx_render_batch_gated) after one forest evaluation and one select, instead of
+        folding the tri-states here level by level. Same results; it falls back to the
+        default path when the phase has no forest, an evaluator has a cache (a hit grants
+        without the rules, which the device cannot see), the context lacks the entry
+        points, or evaluate() is given a producer."""
         from . import runtime
 
         self.config = auth_config
+        self._gated_wanted = gated
+        self._gated = None
         self.ctx = ctx if ctx is not None else runtime.context(device)
         self._rs: Dict[int, object] = {}
         exprs = [auth_config.conditions] + [e for c in auth_config.authorization for e in (c.conditions, c.rules)]
@@ -203,6 +267,17 @@ class AuthPipelineBatch:
             self.key_selectors.append(ValueSelectors(keys, self.ctx, "cache keys") if keys else None)
         dw = auth_config.unauthorized
         self.deny_selectors = ValueSelectors(dw.values(), self.ctx, "denyWith selectors") if dw is not None else None
+        if (gated and self._forest is not None and all(c.cache is None for c in auth_config.authorization)
+                and hasattr(self.ctx, "render_gated_host_arena") and hasattr(self.ctx, "compile_gates")):
+            self._gated = _GatedPhase(self)
+
+    def gate_plan(self, outputs: Sequence[Tuple[int, Optional[jsonexp.Expression]]]) -> GatePlan:
+        """The GatePlan of this AuthConfig over its forest's trees: outputs = [(GATE_*, the
+        output's `when` expression or None)]. Needs the forest (no later priority reads
+        what an earlier one granted)."""
+        col = lambda e: -1 if e is None else self._col[id(e)]  # noqa: E731
+        evs = [(col(c.conditions), col(c.rules), li) for li, level in enumerate(self.levels) for c in level]
+        return GatePlan(col(self.config.conditions), evs, [(on, col(e)) for on, e in outputs], len(set(self._col.values())))
 
     # one launch: expression k of `exprs` on every request in `reqs`
     def _eval(self, exprs: Sequence[jsonexp.Expression], reqs: np.ndarray, arena, offs, lens):
@@ -235,6 +310,9 @@ class AuthPipelineBatch:
 
         if self._needs_regen and producer is None:
             raise ValueError("a later priority selects auth.authorization.*: pass a producer")
+        # (a producer regenerates the documents between priority levels: the default path)
+        if self._gated is not None and producer is None:
+            return self._gated.evaluate([runtime._b(d) for d in docs])
         n = len(docs)
         results = [AuthResult() for _ in range(n)]
         docs = [runtime._b(d) for d in docs]
@@ -429,6 +507,141 @@ class AuthPipelineBatch:
                     headers.update(h)
                     metadata.update(m)
             results[i].headers, results[i].metadata = headers, metadata
+
+
+class GatedSelectors(ResponseSelectors):
+    """One selector ruleset over the union of the response and the denyWith paths."""
+
+    def __init__(self, configs, deny_values, ctx):
+        self.configs = list(configs)
+        self._render = None
+        self.rendered = self.fallbacks = 0
+        ValueSelectors.__init__(self, [v for c in self.configs for v in c.values()] + list(deny_values), ctx,
+                                "response and denyWith selectors")
+
+
+class _GatedPhase:
+    """AuthPipelineBatch(gated=True): one forest evaluation, one select over the union of
+    the response and denyWith paths, one gated render (the verdict and the outputs that
+    apply under it), then the AuthResults the default path gives, field by field."""
+
+    OUT_STRIDE = 2048
+
+    def __init__(self, batch: "AuthPipelineBatch"):
+        from .response import compile_deny_render, compile_render
+
+        self.b = batch
+        cfg, ctx = batch.config, batch.ctx
+        dw = cfg.unauthorized
+        self.sel = GatedSelectors(cfg.response, dw.values() if dw is not None else [], ctx)
+        rops, _ = compile_render(cfg.response, self.sel)
+        self.header_configs = [c for c in cfg.response if c.wrapper == HTTP_HEADER_WRAPPER]
+        outputs = list(rops.outputs)
+        gates = [(GATE_GRANTED, c.conditions) for c in self.header_configs]
+        self.deny_kinds = []
+        if dw is not None:
+            dops, self.deny_kinds = compile_deny_render(dw, self.sel)
+            outputs += dops.outputs
+            gates += [(GATE_DENIED, None)] * len(dops.outputs)
+        self.plan = batch.gate_plan(gates)
+        self.evaluators = [c for level in batch.levels for c in level]
+        self.prog = ctx.compile_render(outputs, len(self.sel.paths))
+        self.gates = ctx.compile_gates(self.plan.top, self.plan.evaluators, self.plan.outputs, self.plan.n_trees)
+
+    def _undecided(self, res):
+        res.undecided, res.code, res.message = True, CODE_UNKNOWN, UNDECIDED_MESSAGE
+
+    def evaluate(self, docs: List[bytes]) -> List[AuthResult]:
+        from .response import RENDER_OK, RENDER_UNRENDERED
+
+        b, cfg, plan, sel = self.b, self.b.config, self.plan, self.sel
+        n = len(docs)
+        results = [AuthResult() for _ in range(n)]
+        if not n:
+            return results
+        lens = np.fromiter((len(d) for d in docs), dtype=np.uint32, count=n)
+        offs = np.zeros(n, dtype=np.uint64)
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        arena = np.frombuffer(b"".join(docs) + b"\0", dtype=np.uint8)
+        tri, err, _ = b.ctx.eval_host_arena([b._forest], arena, offs, lens, with_bitmap=False)
+        tri = np.ascontiguousarray(tri.reshape(n, -1), dtype=np.uint8)
+        err = err.reshape(n, -1)
+        spans = sel.resolve(docs, arena, offs, lens)
+        rec, text, verdicts = b.ctx.render_gated_host_arena(
+            [self.prog], [self.gates], None, arena, offs, lens, spans.spans, tri, text=spans.text,
+            out_stride=self.OUT_STRIDE)
+        dw = cfg.unauthorized
+        deny_slots = sorted({sel._slot[p] for v in dw.values() for p in v.paths()}) if dw is not None else []
+        resp_slots = sorted({sel._slot[p] for c in cfg.response for v in c.values() for p in v.paths()})
+        unresolved = lambda j, slots: bool(slots) and bool(((spans.spans[j, slots, 2] & 0xFF) == 255).any())  # noqa: E731
+        n_hdr = len(self.header_configs)
+        hdr_of = {id(c): k for k, c in enumerate(self.header_configs)}
+        for j, res in enumerate(results):
+            verdict, by = int(verdicts[j, 0]) & 0xFF, int(verdicts[j, 1])
+            if verdict == V_SKIPPED:
+                res.skipped = True
+                continue
+            # the authorization objects of the levels decided before the verdict fell (and of
+            # the denying level: every config of a priority is evaluated)
+            last = plan.evaluators[by][2] if verdict == V_DENIED else None
+            top_undecided = plan.top >= 0 and tri[j, plan.top] == _U
+            for (w, r, prio), c in zip([] if top_undecided else plan.evaluators, self.evaluators):
+                level = [tri[j, t] for ww, rr, pp in plan.evaluators if pp == prio for t in (ww, rr) if t >= 0]
+                if any(t == _U for t in level) or (last is not None and prio > last):
+                    break
+                if (w < 0 or tri[j, w] == _T) and (r < 0 or tri[j, r] == _T):
+                    res.authorization[c.name] = True
+            if verdict == V_UNDECIDED:
+                self._undecided(res)
+                continue
+            out = lambda k: text[j, int(rec[j, k, 0]):int(rec[j, k, 0]) + int(rec[j, k, 1])].tobytes()  # noqa: E731
+            if verdict == V_DENIED:
+                c = self.evaluators[by]
+                r = plan.evaluators[by][1]
+                res.code, res.denied_by = CODE_PERMISSION_DENIED, c.name
+                res.message = b._forest.pattern_error(int(err[j, r])) if tri[j, r] == _E else str(UnauthorizedError())
+                if dw is None:
+                    continue
+                if dw.code:
+                    res.status = dw.code
+                if unresolved(j, deny_slots):
+                    self._undecided(res)
+                    res.authorization = {}
+                    continue
+                values = [v for v in (dw.message, dw.body) if v is not None] + [v for _, v in dw.headers]
+                for k, ((kind, name), v) in enumerate(zip(self.deny_kinds, values)):
+                    st = int(rec[j, n_hdr + k, 2]) & 0xFF
+                    s = (out(n_hdr + k).decode("utf-8") if st == RENDER_OK
+                         else stringify_json(sel.value(v, docs[j], spans[j])))
+                    if kind == "message":
+                        res.message = s
+                    elif kind == "body":
+                        res.body = s
+                    else:
+                        res.deny_headers.append({name: s})
+                continue
+            # granted: the response phase (auth_pipeline.go:490-494)
+            if not cfg.response:
+                continue
+            if unresolved(j, resp_slots):
+                from .runtime import AuthjxError
+
+                raise AuthjxError("device could not resolve a response selector")
+            headers, metadata = {}, {}
+            for level in b.response_levels:
+                for c in level:
+                    if c.conditions is not None and tri[j, b._col[id(c.conditions)]] != _T:
+                        continue  # (an undecided response condition withholds that response only)
+                    k = hdr_of.get(id(c))
+                    st = int(rec[j, k, 2]) & 0xFF if k is not None else RENDER_UNRENDERED
+                    if st == RENDER_OK:
+                        headers[c.wrapper_key] = out(k).decode("utf-8", "replace")
+                    else:
+                        h, m = wrap_responses({c.name: (c, sel.call(c, docs[j], spans[j]))})
+                        headers.update(h)
+                        metadata.update(m)
+            res.headers, res.metadata = headers, metadata
+        return results
 
 
 def evaluate_json_authorization(rules: Optional[jsonexp.Expression], docs: Sequence):

@@ -669,7 +669,8 @@ class ResponseSelectors(ValueSelectors):
 
 # authjx_render_op.op / authjx_rendered.status (include/authjx.h AUTHJX_R_*, AUTHJX_RENDER_*)
 R_LIT, R_STRING, R_STRING_ESC, R_SPRINT, R_MARSHAL = range(5)
-RENDER_OK, RENDER_UNRENDERED = 0, 1
+R_STRINGIFY, R_STRING_UTF8 = 6, 7  # (5 is not assigned)
+RENDER_OK, RENDER_UNRENDERED, RENDER_SKIPPED = 0, 1, 2
 
 
 @dataclass
@@ -739,6 +740,35 @@ def compile_render(configs: Sequence[ResponseConfig], selectors: ValueSelectors)
         outputs.append(ops)
         keys.append(c.wrapper_key)
     return RenderOps(outputs, len(selectors.paths)), keys
+
+
+def compile_deny_render(deny_with, selectors: ValueSelectors) -> Tuple[RenderOps, List[Tuple[str, Optional[str]]]]:
+    """The render program of a denyWith (customizeDenyWith, auth_pipeline.go:581-608) over
+    `selectors`' value slots: one output per value that is set, in the order message, body,
+    each header, every one stringify_json(value.ResolveFor(authJSON)); and what each output
+    is: ("message", None), ("body", None), ("header", name). A static value is rendered
+    here, a template is its literals and R_STRING_UTF8 placeholders (StringifyJSON of a
+    string is the string itself when it is UTF-8), a pattern is R_STRINGIFY."""
+    outputs, kinds = [], []
+    named = [("message", None, deny_with.message), ("body", None, deny_with.body)]
+    named += [("header", name, v) for name, v in deny_with.headers]
+    for kind, name, v in named:
+        if v is None:
+            continue
+        ops: list = []
+        if not v.pattern:
+            _add_lit(ops, stringify_json(v.static).encode())
+        elif v.is_template():
+            for seg, s in template_segments(v.pattern):
+                if seg == "lit":
+                    _add_lit(ops, s.encode())
+                else:
+                    ops.append((R_STRING_UTF8, selectors._slot[s]))
+        else:
+            ops.append((R_STRINGIFY, selectors._slot[v.pattern]))
+        outputs.append(ops)
+        kinds.append((kind, name))
+    return RenderOps(outputs, len(selectors.paths)), kinds
 
 
 def wrap_responses(responses: Dict[str, Tuple[ResponseConfig, object]]):

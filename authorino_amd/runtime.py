@@ -52,8 +52,24 @@ class _RenderOutput(C.Structure):
 
 # authjx_render_op.op (AUTHJX_R_*) and authjx_rendered.status (AUTHJX_RENDER_*)
 R_LIT, R_STRING, R_STRING_ESC, R_SPRINT, R_MARSHAL = range(5)
-RENDER_OK, RENDER_UNRENDERED = 0, 1
+R_STRINGIFY, R_STRING_UTF8 = 6, 7  # (5 is not assigned)
+RENDER_OK, RENDER_UNRENDERED, RENDER_SKIPPED = 0, 1, 2
 RENDER_NO_PROGRAM = 0xFFFFFFFF  # a prog_of_req entry (AUTHJX_RENDER_NO_PROGRAM)
+# authjx_verdict.verdict (AUTHJX_V_*) and authjx_gate_output.on (AUTHJX_GATE_*)
+V_SKIPPED, V_GRANTED, V_DENIED, V_UNDECIDED = range(4)
+GATE_ALWAYS, GATE_GRANTED, GATE_DENIED = range(3)
+
+
+class _GateEvaluator(C.Structure):
+    _fields_ = [("when_tree", C.c_int32), ("rules_tree", C.c_int32), ("priority", C.c_int32)]
+
+
+class _GateOutput(C.Structure):
+    _fields_ = [("on", C.c_uint8), ("when_tree", C.c_int32)]
+
+
+class _Verdict(C.Structure):
+    _fields_ = [("verdict", C.c_uint8), ("reserved", C.c_uint8 * 3), ("denied_by", C.c_int32)]
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -72,6 +88,8 @@ EXPORTS = [
     "authjx_render_compile", "authjx_render_free", "authjx_render_outputs", "authjx_render_batch_device",
     "authjx_render_batch", "authjx_render_batch_multi_device",
     "authjx_phase_create", "authjx_phase_free", "authjx_phase_outputs", "authjx_batcher_phase",
+    "authjx_gates_compile", "authjx_gates_free", "authjx_verdict_of", "authjx_render_batch_gated_device",
+    "authjx_render_batch_gated", "authjx_phase_create_gated", "authjx_batcher_phase_gated",
 ]
 
 
@@ -224,6 +242,34 @@ def load_library(path: str = LIB_PATH):
             L.authjx_batcher_phase.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64,
                                                C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
             L.authjx_batcher_phase.restype = C.c_int
+        if os.environ.get("AUTHJX_LIB") is None or hasattr(L, "authjx_render_batch_gated_device"):
+            L.authjx_gates_compile.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_GateEvaluator), C.c_uint32,
+                                               C.POINTER(_GateOutput), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
+                                               C.c_char_p, C.c_size_t]
+            L.authjx_gates_compile.restype = C.c_int
+            L.authjx_gates_free.argtypes = [C.c_void_p]
+            L.authjx_gates_free.restype = None
+            L.authjx_verdict_of.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(_Verdict)]
+            L.authjx_verdict_of.restype = C.c_int
+            multi = [C.c_void_p, C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p]
+            L.authjx_render_batch_gated_device.argtypes = multi + [
+                C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32,
+                C.c_void_p, C.c_void_p, C.c_void_p]
+            L.authjx_render_batch_gated_device.restype = C.c_int
+            L.authjx_render_batch_gated.argtypes = multi + [
+                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_void_p,
+                C.c_uint32, C.c_void_p, C.c_void_p]
+            L.authjx_render_batch_gated.restype = C.c_int
+        if os.environ.get("AUTHJX_LIB") is None or hasattr(L, "authjx_batcher_phase_gated"):
+            L.authjx_phase_create_gated.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+            L.authjx_phase_create_gated.restype = C.c_int
+            L.authjx_batcher_phase_gated.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint64,
+                                                     C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_void_p,
+                                                     C.c_void_p, C.POINTER(_Verdict)]
+            L.authjx_batcher_phase_gated.restype = C.c_int
         L.authjx_debug_last_error.argtypes = []
         L.authjx_debug_last_error.restype = C.c_char_p
         _lib = L
@@ -500,6 +546,64 @@ class Context:
         rec[:, :, 2] &= 0xFF  # (status is a byte; the three after it are reserved)
         return rec[:n, :prog.n_outputs], out_text
 
+    def compile_gates(self, top_when_tree: int, evaluators, outputs, n_trees: int) -> "Gates":
+        """authjx_gates_compile: evaluators = [(when_tree, rules_tree, priority)], outputs =
+        [(GATE_*, when_tree)], a tree of -1 standing for none."""
+        return Gates(self, top_when_tree, evaluators, outputs, n_trees)
+
+    def render_gated_device(self, progs, gates, prog_of_req, arena, offs, lens, values, out_text, out, tristate,
+                            text=None, tri_of_req=None, verdicts=None, stream=None) -> None:
+        """authjx_render_batch_gated_device on HBM-resident torch tensors: render_multi_device
+        under gates[i] (Gates, or None: program i is ungated) over tristate u8[rows][tri_stride]
+        (row tri_of_req[r], or r); verdicts i32[n][2] or None. Asynchronous."""
+        n = int(lens.numel())
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        parr = (C.c_void_p * max(len(progs), 1))(*[p._h.value if p is not None else None for p in progs])
+        garr = (C.c_void_p * max(len(gates), 1))(*[g._h.value if g is not None else None for g in gates])
+        rc = load_library().authjx_render_batch_gated_device(
+            self._h, parr, len(progs), ptr(prog_of_req), ptr(arena), ptr(offs), ptr(lens), n, ptr(values),
+            int(values.shape[1]), ptr(text), int(text.shape[1]) if text is not None else 0, ptr(out_text),
+            int(out_text.shape[1]), ptr(out), int(out.shape[1]) if out is not None else 0, garr, ptr(tristate),
+            int(tristate.shape[1]) if tristate is not None else 0, ptr(tri_of_req), ptr(verdicts),
+            C.c_void_p(stream) if stream else None)
+        _check(rc, "authjx_render_batch_gated_device")
+
+    def render_gated_host_arena(self, progs, gates, prog_of_req, arena, offs, lens, values, tristate, text=None,
+                                tri_of_req=None, out_stride: int = 4096, out_text=None, records=None, verdicts=None):
+        """authjx_render_batch_gated: (records u32[n][records_stride][3], out_text
+        u8[n][out_stride], verdicts i32[n][2] = {verdict, denied_by}). out_text / records /
+        verdicts: the caller's buffers (what the kernel does not write is kept), else fresh
+        ones; the status and verdict bytes are left unmasked."""
+        n = int(lens.shape[0])
+        arena = np.ascontiguousarray(arena, dtype=np.uint8)
+        if arena.nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dtype=dt)  # noqa: E731
+        text, tristate = opt(text, np.uint8), opt(tristate, np.uint8)
+        prog_of_req, tri_of_req = opt(prog_of_req, np.uint32), opt(tri_of_req, np.uint32)
+        if out_text is None:
+            out_text = np.zeros((max(n, 1), out_stride), dtype=np.uint8)
+        if records is None:
+            records = np.zeros((max(n, 1), max([p.n_outputs for p in progs if p is not None] + [1]), 3), dtype=np.uint32)
+        if verdicts is None:
+            verdicts = np.zeros((max(n, 1), 2), dtype=np.int32)
+        for a in (out_text, records, verdicts):
+            assert a.flags.c_contiguous and a.shape[0] >= n
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None  # noqa: E731
+        parr = (C.c_void_p * max(len(progs), 1))(*[p._h.value if p is not None else None for p in progs])
+        garr = (C.c_void_p * max(len(gates), 1))(*[g._h.value if g is not None else None for g in gates])
+        rc = load_library().authjx_render_batch_gated(
+            self._h, parr, len(progs), ptr(prog_of_req), ptr(arena), int(arena.nbytes), ptr(offs), ptr(lens), n,
+            ptr(values), int(values.shape[1]) if values.ndim == 3 else 0, ptr(text),
+            int(text.shape[1]) if text is not None else 0, ptr(out_text), int(out_text.shape[1]), ptr(records),
+            int(records.shape[1]), garr, ptr(tristate), int(tristate.shape[1]) if tristate is not None else 0,
+            ptr(tri_of_req), ptr(verdicts))
+        _check(rc, "authjx_render_batch_gated")
+        return records, out_text, verdicts
+
     def release_stream(self, stream) -> None:
         """authjx_release_stream: free the workspace kept for a (short-lived) stream."""
         L = load_library()
@@ -574,6 +678,42 @@ class Ruleset:
             self._h = None
 
 
+class Gates:
+    """The gates of a render program (authjx_gates_compile / authjx_gates_free): the verdict
+    fold's plan, on the device for the gated render and on the host for verdict_of."""
+
+    def __init__(self, ctx: Context, top_when_tree: int, evaluators, outputs, n_trees: int):
+        L = load_library()
+        self.ctx = ctx
+        earr = (_GateEvaluator * max(len(evaluators), 1))(*[_GateEvaluator(*(int(x) for x in e)) for e in evaluators])
+        oarr = (_GateOutput * max(len(outputs), 1))(*[_GateOutput(int(on), int(w)) for on, w in outputs])
+        err = C.create_string_buffer(256)
+        h = C.c_void_p()
+        rc = L.authjx_gates_compile(ctx._h, int(top_when_tree), earr, len(evaluators), oarr, len(outputs),
+                                    int(n_trees), C.byref(h), err, 256)
+        if rc != 0:
+            raise AuthjxError(f"authjx_gates_compile failed ({'EINVAL' if rc == -1 else rc}): "
+                              f"{err.value.decode(errors='replace')}")
+        self._h = h
+        self.n_outputs, self.n_trees = len(outputs), int(n_trees)
+
+    def verdict_of(self, tri_row) -> Tuple[int, int]:
+        """authjx_verdict_of: (verdict, denied_by) of one request's tri-states."""
+        t = np.ascontiguousarray(tri_row, dtype=np.uint8)
+        v = _Verdict()
+        _check(load_library().authjx_verdict_of(self._h, C.c_void_p(t.ctypes.data), int(t.shape[0]), C.byref(v)),
+               "authjx_verdict_of")
+        return int(v.verdict), int(v.denied_by)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                load_library().authjx_gates_free(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+
 class RenderProgram:
     """A render program resident in HBM (authjx_render_compile / authjx_render_free): one
     output per response header, each a list of (R_LIT, bytes) | (op, value slot)."""
@@ -618,13 +758,21 @@ class Phase:
     borrowed: this object keeps them alive."""
 
     def __init__(self, ctx: Context, rules: "Ruleset", selectors: "Ruleset", prog: "RenderProgram",
-                 text_stride: int = 4096, out_stride: int = 1024):
+                 text_stride: int = 4096, out_stride: int = 1024, gates: Optional["Gates"] = None):
+        """gates: authjx_phase_create_gated, a phase whose requests take the gated render."""
         h = C.c_void_p()
         ptr = lambda o: o._h if o is not None else None  # noqa: E731
-        rc = load_library().authjx_phase_create(ctx._h if ctx is not None else None, ptr(rules), ptr(selectors),
-                                                ptr(prog), int(text_stride), int(out_stride), C.byref(h))
-        _check(rc, "authjx_phase_create")
+        if gates is None:
+            rc = load_library().authjx_phase_create(ctx._h if ctx is not None else None, ptr(rules), ptr(selectors),
+                                                    ptr(prog), int(text_stride), int(out_stride), C.byref(h))
+            _check(rc, "authjx_phase_create")
+        else:
+            rc = load_library().authjx_phase_create_gated(ctx._h if ctx is not None else None, ptr(rules),
+                                                          ptr(selectors), ptr(prog), ptr(gates), int(text_stride),
+                                                          int(out_stride), C.byref(h))
+            _check(rc, "authjx_phase_create_gated")
         self._h = h
+        self.gates = gates
         self.ctx, self.rules, self.selectors, self.prog = ctx, rules, selectors, prog
         self.text_stride, self.out_stride = int(text_stride), int(out_stride)
         self.n_outputs = int(load_library().authjx_phase_outputs(h))
@@ -765,6 +913,25 @@ class Batcher:
         vals = [out_text[int(s):int(s) + int(ln)].tobytes() if (int(st) & 0xFF) == RENDER_OK else None
                 for s, ln, st in out[:phase.n_outputs]]
         return list(tri), list(err), vals
+
+    def phase_gated(self, phase: "Phase", doc, timeout_s: float = 0.0):
+        """authjx_batcher_phase_gated: (tri-states, error indices, [(status, bytes) per output],
+        (verdict, denied_by)) of one document."""
+        d = _b(doc)
+        nt = max(1, len(phase.rules.offsets))
+        tri = (C.c_uint8 * nt)()
+        err = (C.c_int32 * nt)()
+        out_text = np.zeros(phase.out_stride, dtype=np.uint8)
+        out = np.zeros((max(phase.n_outputs, 1), 3), dtype=np.uint32)
+        v = _Verdict(255, (C.c_uint8 * 3)(), 0)
+        rc = load_library().authjx_batcher_phase_gated(self._h, phase._h, d, len(d), int(timeout_s * 1e6), tri, err,
+                                                       C.c_void_p(out_text.ctypes.data), C.c_void_p(out.ctypes.data),
+                                                       C.byref(v))
+        if rc == -5:
+            raise BatchTimeout("authjx_batcher_phase_gated: deadline passed")
+        _check(rc, "authjx_batcher_phase_gated")
+        vals = [(int(st) & 0xFF, out_text[int(s):int(s) + int(ln)].tobytes()) for s, ln, st in out[:phase.n_outputs]]
+        return list(tri), list(err), vals, (int(v.verdict), int(v.denied_by))
 
     def phase_loadgen(self, phases, phase_of_req, arena, offs, lens, threads: int = 64):
         """Profiling: authjx_debug_phase_loadgen, `threads` native producer threads calling

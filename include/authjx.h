@@ -389,8 +389,23 @@ int authjx_pack_json(const uint8_t* tapes, const uint64_t* tape_offs, const uint
 #define AUTHJX_R_STRING_ESC 2
 #define AUTHJX_R_SPRINT 3
 #define AUTHJX_R_MARSHAL 4
+/*   AUTHJX_R_STRINGIFY   json.StringifyJSON(Result.Value()) (pkg/json/json.go:153-159), a
+ *                        denyWith message / body / header: a string's Result.String() bytes; a
+ *                        number as FormatFloat(ParseFloat(raw), 'f', -1, 64) whatever its
+ *                        spelling (12345678901234567890123 -> 12345678901234568000000, +-Inf:
+ *                        the output is empty, status OK); true / false; null: nothing; an
+ *                        object / array as MARSHAL writes it. Declines as MARSHAL does
+ *   AUTHJX_R_STRING_UTF8 STRING that declines when the value's bytes are not UTF-8 (a
+ *                        template placeholder under StringifyJSON, where Go writes U+FFFD) */
+/* (op 5 is not assigned: authjx_render_compile answers AUTHJX_EINVAL for it, as before the
+ * two ops above existed) */
+#define AUTHJX_R_STRINGIFY 6
+#define AUTHJX_R_STRING_UTF8 7
 #define AUTHJX_RENDER_OK 0
 #define AUTHJX_RENDER_UNRENDERED 1
+/* the output does not apply under the request's verdict (the gated calls below): nothing
+ * appended, none of its values read; its record is {write position, 0, SKIPPED} */
+#define AUTHJX_RENDER_SKIPPED 2
 typedef struct authjx_render authjx_render;
 typedef struct {
     uint8_t op;         /* AUTHJX_R_* */
@@ -450,6 +465,79 @@ int authjx_render_batch_multi_device(authjx_ctx* ctx, const authjx_render* const
                                      uint8_t* d_out_text, uint32_t out_stride, authjx_rendered* d_out,
                                      uint32_t records_stride, void* stream);
 
+/* ---- gated render: the verdict folded on the device, outputs chosen by it ------------
+ * The fold of auth_pipeline.go's `when` gates and authorization phase over a request's
+ * tri-states t[0, n_trees) (an authjx_compile_forest evaluation: one entry per expression):
+ *   1. t[top_when_tree] UNDECIDED: the verdict is UNDECIDED; else not T: SKIPPED.
+ *   2. The evaluators by priority level (runs of equal priority, in list order). A level
+ *      that names an UNDECIDED tree (a `when` or rules, also the rules of an evaluator whose
+ *      `when` is not met): UNDECIDED. Else its first evaluator whose `when` is absent or T
+ *      and whose rules exist and are not T: DENIED, denied_by = its index; the fold stops.
+ *   3. No level denies: GRANTED.
+ * denied_by is -1 unless the verdict is DENIED. Output k of the render program then
+ *   ALWAYS   renders;
+ *   GRANTED  renders when the verdict is GRANTED and its when_tree is absent or T; is
+ *            AUTHJX_RENDER_UNRENDERED when the verdict is GRANTED and that tree UNDECIDED;
+ *   DENIED   renders when the verdict is DENIED;
+ * under an UNDECIDED verdict every output but ALWAYS is AUTHJX_RENDER_UNRENDERED (the
+ * caller's own evaluator decides such a request); every other output is
+ * AUTHJX_RENDER_SKIPPED. A tree index of -1 stands for "none". */
+#define AUTHJX_V_SKIPPED 0 /* the AuthConfig's `when` is not met: OK, no outputs */
+#define AUTHJX_V_GRANTED 1
+#define AUTHJX_V_DENIED 2
+#define AUTHJX_V_UNDECIDED 3
+typedef struct {
+    int32_t when_tree, rules_tree, priority;
+} authjx_gate_evaluator;
+#define AUTHJX_GATE_ALWAYS 0
+#define AUTHJX_GATE_GRANTED 1
+#define AUTHJX_GATE_DENIED 2
+typedef struct {
+    uint8_t on; /* AUTHJX_GATE_* */
+    int32_t when_tree;
+} authjx_gate_output;
+typedef struct {
+    uint8_t verdict; /* AUTHJX_V_* */
+    uint8_t reserved[3];
+    int32_t denied_by;
+} authjx_verdict;
+typedef struct authjx_gates authjx_gates;
+/* AUTHJX_EINVAL (and a message in errbuf): a tree index >= n_trees or below -1, priorities
+ * that are not non-decreasing, an ALWAYS output with a when_tree, an unknown `on`. */
+int authjx_gates_compile(authjx_ctx* ctx, int32_t top_when_tree, const authjx_gate_evaluator* evaluators,
+                         uint32_t n_evaluators, const authjx_gate_output* outputs, uint32_t n_outputs,
+                         uint32_t n_trees, authjx_gates** out, char* errbuf, size_t errcap);
+void authjx_gates_free(authjx_gates* gates);
+/* The same fold on the host (the function the kernel runs): tristate[0, n_trees), n_trees at
+ * least the gates' own. */
+int authjx_verdict_of(const authjx_gates* gates, const uint8_t* tristate, uint32_t n_trees, authjx_verdict* out);
+/* authjx_render_batch_multi_device under gates: request r renders progs[d_prog_of_req[r]]
+ * under gates[d_prog_of_req[r]] (a NULL entry: every output renders, no verdict is
+ * written), folding d_tristate[(d_tri_of_req ? d_tri_of_req[r] : r) * tri_stride ...], where
+ * an evaluation on the same stream left it. An output that does not apply is decided before
+ * its first value is read. d_out_verdict (may be NULL): one authjx_verdict per request that
+ * has a program and gates. The checks of the multi call, and AUTHJX_EINVAL as well for a
+ * gates object whose n_outputs differs from its program's, whose n_trees exceeds tri_stride
+ * or of another device, and for a NULL d_tristate when any gates entry is not NULL. */
+int authjx_render_batch_gated_device(authjx_ctx* ctx, const authjx_render* const* progs, uint32_t n_progs,
+                                     const uint32_t* d_prog_of_req, const uint8_t* d_arena, const uint64_t* d_offs,
+                                     const uint32_t* d_lens, uint32_t n, const authjx_value* d_values,
+                                     uint32_t values_stride, const uint8_t* d_text, uint32_t text_stride,
+                                     uint8_t* d_out_text, uint32_t out_stride, authjx_rendered* d_out,
+                                     uint32_t records_stride, const authjx_gates* const* gates,
+                                     const uint8_t* d_tristate, uint32_t tri_stride, const uint32_t* d_tri_of_req,
+                                     authjx_verdict* d_out_verdict, void* stream);
+/* Same from host buffers (prog_of_req, tristate and tri_of_req too; tristate holds n rows,
+ * or one more than the largest tri_of_req entry); synchronous. out / out_verdict entries
+ * the kernel does not write keep the caller's bytes. */
+int authjx_render_batch_gated(authjx_ctx* ctx, const authjx_render* const* progs, uint32_t n_progs,
+                              const uint32_t* prog_of_req, const uint8_t* arena, uint64_t arena_len,
+                              const uint64_t* offs, const uint32_t* lens, uint32_t n, const authjx_value* values,
+                              uint32_t values_stride, const uint8_t* text, uint32_t text_stride, uint8_t* out_text,
+                              uint32_t out_stride, authjx_rendered* out, uint32_t records_stride,
+                              const authjx_gates* const* gates, const uint8_t* tristate, uint32_t tri_stride,
+                              const uint32_t* tri_of_req, authjx_verdict* out_verdict);
+
 /* ---- micro-batcher: a phase's response outputs with each decision -------------------
  * One AuthConfig as the serving path sees it: `rules` (authjx_compile or _forest: what
  * authjx_batcher_eval takes), `selectors` (authjx_compile, patterns {path, EQ, ""}, root -1:
@@ -482,6 +570,24 @@ uint32_t authjx_phase_outputs(const authjx_phase* ph);
 int authjx_batcher_phase(authjx_batcher* b, const authjx_phase* ph, const uint8_t* doc, size_t len,
                          uint64_t timeout_us, uint8_t* out_tristate, int32_t* out_err_idx,
                          uint8_t* out_text, authjx_rendered* out);
+
+/* A phase under gates (authjx_gates_compile over the trees of `rules`): its requests take
+ * the gated render, so only the outputs that apply under the request's verdict are rendered
+ * (the others AUTHJX_RENDER_SKIPPED, no bytes) and the verdict comes back with them. The
+ * batch's tri-states are read where the evaluation left them in device memory. A batch that
+ * mixes gated and ungated phases takes one gated launch per stride group (an ungated
+ * phase's requests render every output, as before). `gates` is borrowed like the other
+ * three. AUTHJX_EINVAL: authjx_phase_create's cases; gates whose n_outputs differs from the
+ * program's, whose n_trees exceeds the rules' trees, or of another device. */
+int authjx_phase_create_gated(authjx_ctx* ctx, const authjx_ruleset* rules, const authjx_ruleset* selectors,
+                              const authjx_render* prog, const authjx_gates* gates, uint32_t text_stride,
+                              uint32_t out_stride, authjx_phase** out);
+/* authjx_batcher_phase on a gated phase, with the verdict (out_verdict may be NULL).
+ * AUTHJX_EINVAL for an ungated phase. authjx_batcher_phase itself also accepts a gated
+ * phase (the same outputs, no verdict) and is unchanged for an ungated one. */
+int authjx_batcher_phase_gated(authjx_batcher* b, const authjx_phase* ph, const uint8_t* doc, size_t len,
+                               uint64_t timeout_us, uint8_t* out_tristate, int32_t* out_err_idx,
+                               uint8_t* out_text, authjx_rendered* out, authjx_verdict* out_verdict);
 
 #ifdef __cplusplus
 }
